@@ -5,19 +5,30 @@ One step = one batched launch of the ripple-carry adder (src/impls/numbers/commo
 `--batch` u32 ciphertext pairs per GPU (BASELINE.json configs[1]: batch 4096), inputs already
 resident in HBM.  Multi-GPU: one process per GPU (torchrun), each rank adds its own shard (weak
 scaling, no data-path collective); keys are broadcast once over RCCL at setup, and after the timed
-region the decrypted results are gathered over RCCL (all_gather) and checked on rank 0.
+region the ranks' wall times (with `--full` the decrypted results too, checked on rank 0) are
+gathered over RCCL (all_gather).
 
 `--workload mixed` runs configs[4] instead: one u32 add plus one u32 multiply (low 8 result bits)
-per value at d = dp = tau = 256, global batch 2^20 split over the ranks (strong scaling).
+per value at d = dp = tau = 256, global batch 2^20 split over the ranks (strong scaling); its
+line always carries the check of every sum and product (`verified`).
 
 `--gpus N` with N > 1 and no torchrun environment starts N rank processes itself (one per GPU,
 before this process touches the GPU) and exits with their status; under torchrun it checks that
 WORLD_SIZE equals N.  `--workload distcheck` runs only the multi-rank plumbing (spawn, key
 broadcast, shards, result gather, max-over-ranks time) on the CPU with gloo, for the CPU tests.
 
-Prints ONE JSON line (rank 0).  Besides the contract fields it carries
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and
+prints ONE JSON line (rank 0): the contract fields (`value`, `ms_per_step`, ...) and
   roofline      MFMA roofline of the dominant kernel (the carry chain on fp4 matrix cores):
                 algorithmic bit-pair ops per launch / its HIP-event duration, vs the dense fp4 peak
+                (from the device stamps of the timed steps themselves: no run of its own)
+`--dump-outputs DIR` also writes what the last timed step computed as DIR/<name>.npy (float32 /
+float64, a fixed seeded sample of the values where the whole output is too big), so that two
+builds can be compared output for output: with the same arguments the inputs are identical.
+
+`--full` adds everything that takes runs or checks of its own:
+  verified      the sums decrypted on the device and compared with the plaintext sums
+  roofline.sustained  the chain kernel at sustained clocks (the K-step graph replayed again)
   cpu_baseline  the CPU oracle (operation-for-operation restatement of the reference) timed on a
                 bounded sample on this host: one thread (the reference is single-threaded) and
                 all host cores (values split over OpenMP threads), CPU model stated
@@ -190,10 +201,47 @@ def gather_results(world, device, res, wall):
     res = res.to(device)
     parts = [torch.empty_like(res) for _ in range(world)]
     dist.all_gather(parts, res.contiguous())
-    w = torch.tensor([float(wall)], dtype=torch.float64, device=device)
+    return torch.cat(parts).cpu().numpy(), max_wall(world, device, wall)
+
+
+def max_wall(world, device, wall):
+    """The timed region's wall time as `value` uses it: the max over the ranks (all_gather; a
+    plain run gathers this alone, not the results)."""
+    if world == 1:
+        return float(wall)
+    w = torch.tensor([float(wall)], dtype=torch.float64, device=coll_device(device))
     walls = [torch.empty_like(w) for _ in range(world)]
     dist.all_gather(walls, w)
-    return torch.cat(parts).cpu().numpy(), max(float(x.item()) for x in walls)
+    return max(float(x.item()) for x in walls)
+
+
+DUMP_BUDGET = 24 << 20  # bytes of .npy per dumped batch (--dump-outputs: under 64 MB in all)
+
+
+def dump_batch(path, name, c):
+    """--dump-outputs: the device batch `c` (this rank's ciphertexts, as a caller of the timed
+    path holds them after its last step) as
+      <name>_values.npy  float64 (k,)          the values written: all n, or a fixed seeded
+                                               sample of them within DUMP_BUDGET
+      <name>_limbs.npy   float32 (k, 8*stride) their limbs as little-endian bytes, one float per
+                                               byte (exact; a one-bit difference is a difference
+                                               of at least 1 in 255)
+      <name>_degree.npy  float32 (k, nbits)    their exact degrees
+      <name>_bound.npy   float32 (nbits,)      the batch's static per-bit degree bounds (bit i
+                                               holds bound[i] // 64 + 1 limbs of a value's
+                                               stride, in bit order)."""
+    os.makedirs(path, exist_ok=True)
+    stride = c.stride
+    k = max(1, min(c.n, DUMP_BUDGET // (4 * (8 * stride + c.nbits) + 8)))
+    idx = np.sort(np.random.default_rng(BENCH_SEED).choice(c.n, size=k, replace=False))
+    sel = torch.from_numpy(idx).to(c.limbs.device)
+    rows = c.limbs.view(c.n, stride)[sel].cpu().numpy().view(np.uint64)
+    limbs = np.ascontiguousarray(rows.astype("<u8")).view(np.uint8).reshape(k, 8 * stride)
+    deg = c.degree.view(c.n, c.nbits)[sel].cpu().numpy().view(np.uint32)
+    np.save(os.path.join(path, name + "_values.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, name + "_limbs.npy"), limbs.astype(np.float32))
+    np.save(os.path.join(path, name + "_degree.npy"), deg.astype(np.float32))
+    np.save(os.path.join(path, name + "_bound.npy"), c.bound.astype(np.float32))
 
 
 def time_loop(fn, steps, warmup, world, stream=None):
@@ -933,13 +981,20 @@ def run_add(args, world, rank, device):
         chain_src = (f"device wall-clock stamps of each of the timed region's {chain_n} chain "
                      "launches (direct launches; hm_ctx_set_kernel_timing)")
     ctx.synchronize()  # raises on any device-side error flag
+    if args.dump_outputs and rank == 0:  # the last timed step's output, before anything reruns it
+        dump_batch(args.dump_outputs, "add_out", out)
     sustained = sustained_chain(ctx, lambda: H.add_into(ctx, ca, cb, out), args.steps, n,
-                                chain_bit_pairs(ca.bound, cb.bound)) if args.graph else None
-    # verification (untimed): decrypt on device, gather the plaintexts over RCCL, check on rank 0
-    got, wall = gather_results(world, device, ctx.decrypt_bytes(out), wall)
-    want = np.concatenate([sum(shard_inputs(r, n)).astype(np.uint32) for r in range(world)])
-    got = got.view("<u4").reshape(-1)
-    correct = int(np.sum(got == want))
+                                chain_bit_pairs(ca.bound, cb.bound)) \
+        if args.full and args.graph else None
+    got = correct = None
+    if args.full:
+        # verification (untimed): decrypt on device, gather the plaintexts over RCCL, check on rank 0
+        got, wall = gather_results(world, device, ctx.decrypt_bytes(out), wall)
+        want = np.concatenate([sum(shard_inputs(r, n)).astype(np.uint32) for r in range(world)])
+        got = got.view("<u4").reshape(-1)
+        correct = int(np.sum(got == want))
+    else:
+        wall = max_wall(world, device, wall)
     total = n * world * args.steps
 
     in_bytes = 8 * (ca.stride + cb.stride)
@@ -978,7 +1033,6 @@ def run_add(args, world, rank, device):
                    "add_chain": args.add_chain,
                    "batch_per_gpu": n, "d": PARAMS[0], "dp": PARAMS[1], "delta": PARAMS[2],
                    "tau": PARAMS[3], "parallelism": f"batch-sharded x{world}"},
-        "verified": {"correct_sums": correct, "of": n * world},
         "roofline": {"bound": "mfma", "achieved": achieved, "peak": FP4_MFMA_PEAK_TFLOPS,
                      "unit": "TFLOP/s", "frac": achieved / FP4_MFMA_PEAK_TFLOPS, "traffic": traffic,
                      "kernel": "add_chain_mfma_kernel (carry products as {0,1} Toeplitz GEMMs on "
@@ -1002,6 +1056,9 @@ def run_add(args, world, rank, device):
                              "profiles/add_traffic.json (rocprofv3 --pmc passes of this bench "
                              "command), not measured in this run"},
     }
+    if not args.full:  # a plain run: the headline and nothing that takes a run of its own
+        return result
+    result["verified"] = {"correct_sums": correct, "of": n * world}
     if sustained:
         result["roofline"]["sustained"] = sustained
     if rank == 0 and world == 1 and not args.no_cpu:
@@ -1021,7 +1078,7 @@ class MixedWorkload:
     """configs[4]'s per-rank state: keys (rank 0's, broadcast), this rank's shard of the global
     batch encrypted, the output batches, and the launch chunks.  `step()` is one pass of the
     workload: per chunk of MIXED_CHUNK values one u32 add and one u32 multiply reduced to its low
-    MUL_LOW_K result bits.  Shared by run_mixed, the default bench's `secondary` line and the
+    MUL_LOW_K result bits.  Shared by run_mixed, the `--full` bench's `secondary` line and the
     full-batch test (tests/test_gpu_properties.py)."""
 
     def __init__(self, world, rank, device, glob):
@@ -1078,6 +1135,9 @@ def run_mixed(args, world, rank, device):
     w = MixedWorkload(world, rank, device, glob)
     wall, ev_s = time_loop(w.step, args.steps, args.warmup, world, w.ctx.stream)
     w.ctx.synchronize()
+    if args.dump_outputs and rank == 0:
+        dump_batch(args.dump_outputs, "mixed_sums", w.sums)
+        dump_batch(args.dump_outputs, "mixed_products", w.prods)
     ok_s, ok_p, wall = w.verify(device, wall)
     total = glob * args.steps
     return {
@@ -1139,9 +1199,14 @@ def main():
                     help="add: configs[1] (headline); mixed: configs[4]; distcheck: CPU plumbing")
     ap.add_argument("--batch", type=int, default=0,
                     help="add: u32 pairs per GPU (default 4096); mixed: global batch (2^20)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="add: also check the sums, replay the chain at sustained clocks, time the "
+                         "CPU oracle and run every secondary line (minutes); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0's shard)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: no CPU oracle leg")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: no secondary lines")
     ap.add_argument("--add-chain", choices=["auto", "mfma", "valu"], default="auto",
                     help="hm_ctx_set_add_options (auto = the MFMA chain where it applies)")
     ap.add_argument("--add-pipeline", type=int, default=0,

@@ -4,7 +4,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/${1:-abpipe}; mkdir -p $OUT
 for r in 1 2 3; do for p in 1 0; do
-  timeout -k 10 120 python3 -u bench.py --no-secondary --no-cpu --add-pipeline $p > $OUT/b_${p}_$r.log 2>&1 || exit 1
+  timeout -k 10 120 python3 -u bench.py --full --no-secondary --no-cpu --add-pipeline $p > $OUT/b_${p}_$r.log 2>&1 || exit 1
   python3 - $OUT/b_${p}_$r.log $p <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

@@ -1,6 +1,6 @@
 #!/bin/bash
 # The round-end checks in one GPU call: the whole -m gpu suite, smoke(), and the driver's default
-# bench command (python3 bench.py --gpus 1 --steps 20 --warmup 5) with its secondary lines.
+# bench command with its secondary lines (python3 bench.py --full --gpus 1 --steps 20 --warmup 5).
 # usage: scripts/gpu_full.sh tag
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
@@ -12,7 +12,7 @@ timeout -k 10 1000 python -u -m pytest tests -m gpu -x -v --timeout 400 --timeou
 rc=$?; grep -E "FAILED|ERROR|passed|failed" $OUT/pytest.log | tail -20; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 python3 -u -c "import __graft_entry__ as g; g.smoke(); print('SMOKE OK')" > $OUT/smoke.log 2>&1 || { tail -5 $OUT/smoke.log; exit 1; }
 tail -1 $OUT/smoke.log
-timeout -k 10 400 python3 -u bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+timeout -k 10 400 python3 -u bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
 python3 - <<PY
 import json
 d = json.loads(open("$OUT/bench.json").read().strip().splitlines()[-1])
