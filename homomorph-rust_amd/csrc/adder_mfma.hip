@@ -81,19 +81,21 @@ template <int NC> constexpr int kPrefetchOf = NC > 16 ? HM_MFMA_PREFETCH25 : NC 
 // tiles
 template <int NC> constexpr int kStage(int k) { return NC <= 8 ? 2 * k : 1 + 3 * k; }
 template <int NC, class Side, int kPrefetch = kPrefetchOf<NC>>
-__device__ __forceinline__ v16f tile_mfma(const v8i (&Af)[NC], const uint4 *rb, const uint4 *rbn,
-                                          uint4 (&pf)[kPrefetch], v16f acc, Side &&side) {
-    // pf holds this tile's first kPrefetch B fragments (read during the tile before); the last
-    // kPrefetch reads of this tile fetch the next tile's (window base rbn; its ring fill is side
-    // stage 2, issued above them), so the next tile's first MFMA does not wait for the LDS
+__device__ __forceinline__ v16f tile_mfma(const v8i (&Af)[NC], uint32_t rb, uint32_t rbn,
+                                          u32x4 (&pf)[kPrefetch], v16f acc, Side &&side) {
+    // rb, rbn: LDS byte addresses of this tile's and the next tile's window (one VGPR each; the
+    // chunks are immediate offsets).  pf holds this tile's first kPrefetch B fragments (read
+    // during the tile before); the last kPrefetch reads of this tile fetch the next tile's (its
+    // ring fill is side stage 2, issued above them), so the next tile's first MFMA does not wait
+    // for the LDS
     static_assert(NC - kPrefetch > kStage<NC>(2), "next tile's B reads must follow its ring fill (stage 2)");
-    uint4 bq[NC];
+    u32x4 bq[NC];
 #pragma unroll
     for (int c = 0; c < kPrefetch; ++c) bq[c] = pf[c];
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
-        if (c + kPrefetch < NC) bq[c + kPrefetch] = rb[2 * (c + kPrefetch)];
-        else pf[c + kPrefetch - NC] = rbn[2 * (c + kPrefetch - NC)];
+        if (c + kPrefetch < NC) bq[c + kPrefetch] = lds_at<const u32x4>(rb)[2 * (c + kPrefetch)];
+        else pf[c + kPrefetch - NC] = lds_at<const u32x4>(rbn)[2 * (c + kPrefetch - NC)];
         const v8i Bf = {(int)bq[c].x, (int)bq[c].y, (int)bq[c].z, (int)bq[c].w, 0, 0, 0, 0};
         acc = mfma_fp4(Af[c], Bf, acc);
         asm volatile("" : "+v"(acc)::"memory");
@@ -104,37 +106,21 @@ __device__ __forceinline__ v16f tile_mfma(const v8i (&Af)[NC], const uint4 *rb, 
     return acc;
 }
 
-// Ring slot of carry word w: its nibble image at slot w % kMfmaRingSlots, and slots below
-// kMirror once more past the end, so a tile's window [slot, slot + 2*NC - 1) is contiguous
-// wherever it starts: its B reads share one address and differ by immediates.
-template <int kMirror>
-__device__ __forceinline__ void ring_put(uint32_t *ring, int w, int h, uint2 nb) {
-    const int s = w & (kMfmaRingSlots - 1);
-    uint32_t *slot = &ring[s * 4 + 2 * h];
-    *(uint2 *)slot = nb;
-    if (kMirror >= kMfmaRingSlots || s < kMirror) *(uint2 *)(slot + 4 * kMfmaRingSlots) = nb;
-}
-
-// Nibble images of carry words [base, base + count) into the ring (count <= 64).  Lane l writes
-// bytes 2h, 2h+1 of word base + k (k = l/2 + 32*pass, h = l%2) as two table lookups: a lane pair
-// fills one 16-byte slot, so a wave's 8-byte stores are contiguous (no LDS bank conflicts; lane
-// halves h = l/32 wrote 16-byte-strided pieces, two-way conflicted)
-#ifndef HM_RING_PAIRS
-#define HM_RING_PAIRS 1 // (A/B knob) 0: lane halves h = l/32 fill the slots' halves
-#endif
-template <int kMirror>
-__device__ __forceinline__ void ring_fill(const uint32_t *C, uint32_t *ring, const uint32_t *tab,
-                                          int base, int count, int lane) {
-    const int h = HM_RING_PAIRS ? lane & 1 : lane >> 5;
-    for (int k = HM_RING_PAIRS ? lane >> 1 : lane & 31; k < count; k += 32) {
-        const int w = base + k;
-        const uint32_t v = C[w] >> (16 * h);
-        uint2 nb;
-        nb.x = tab[v & 0xFFu];
-        nb.y = tab[(v >> 8) & 0xFFu];
-        ring_put<kMirror>(ring, w, h, nb);
-    }
-}
+// Ring slot of carry word w during bit i: (w + D) % kMfmaRingSlots with D = np, the words of P_i
+// (the ring is refilled from its first window on every bit, so its origin may move with the
+// bit).  Slots below kMirror are written once more past the end, so a tile's window
+// [slot, slot + 2*NC - 1) is contiguous wherever it starts: its B reads share one address and
+// differ by immediates.  With this origin tile T's window starts at slot 32 (T % 4) + col + h and
+// the 32 words staged for tile T - 1 fill slots 32 ((T - 1) % 4) .. + 31 exactly: which quarter
+// ("phase") of the ring a tile reads and fills, and whether the fill needs the mirror copy, are
+// wave-uniform, so the tile loop derives both addresses from a scalar phase with one v_add each
+// (with the origin at word 0 the slots wrapped inside a wave: an add, a mask and a shift per
+// address and a per-lane compare with an EXEC round trip for the mirror).
+// A phase is filled by lane pairs: lane l writes the nibble images of bytes 2h, 2h + 1 of word
+// l/2 (h = l%2) as two table lookups, so a lane pair fills one 16-byte slot and a wave's 8-byte
+// stores are contiguous (no LDS bank conflicts; lane halves h = l/32 wrote 16-byte-strided pieces,
+// two-way conflicted).
+constexpr uint32_t kPhaseBytes = 16u * 32u; // 32 slots
 
 // Wait for bit i's record DMA (stage_rec) but not for the `young` sum stores the previous bit's
 // tiles issued after it: gfx9 vector memory operations complete in order, loads and stores alike
@@ -151,6 +137,13 @@ __device__ __forceinline__ void wait_record(int young) {
     else if (young >= 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     else if (young >= 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
+}
+
+// One sum word to global memory at a wave-uniform base (SGPR pair) plus a 32-bit lane offset:
+// the SGPR-base form of global_store_dword (a store like the compiler's own: nothing waits on it
+// but the next bit's vmcnt wait and the end of the kernel)
+__device__ __forceinline__ void sum_store(uint64_t base, uint32_t off, uint32_t v) {
+    asm volatile("global_store_dword %0, %1, %2" : : "v"(off), "v"(v), "s"(base) : "memory");
 }
 
 // waves per block (<= kAddWavesPerBlock, which the host plan's LDS check assumes)
@@ -317,11 +310,13 @@ add_chain_mfma_kernel(AddArgs A) {
         // lane, chunk c at +8c words (immediate offsets), one shift for all chunks
         v8i Af[NC];
         const int jb = 32 * (kRevWords - D + h) - 1 - row_bit(col); // (row-permuted tiles)
-        const uint32_t *rw0 = RS + (jb >> 3);
+        // (an opaque address: every one of the NC x 5 words is an immediate offset of it; with
+        // RS's offset folded into the immediates most of the ds_read2_b32 needed a v_add)
+        const uint32_t rw0 = lds_opaque(lds_addr(RS) + 4u * (uint32_t)(jb >> 3));
         const uint32_t sh = 4u * (uint32_t)(jb & 7);
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
-            const uint32_t *rw = rw0 + 8 * c;
+            const HM_LDS uint32_t *rw = lds_at<const uint32_t>(rw0) + 8 * c;
             const uint32_t w0 = rw[0], w1 = rw[1], w2 = rw[2], w3 = rw[3], w4 = rw[4];
             Af[c] = (v8i){(int)funnel(w1, w0, sh), (int)funnel(w2, w1, sh), (int)funnel(w3, w2, sh),
                           (int)funnel(w4, w3, sh), 0, 0, 0, 0};
@@ -332,11 +327,11 @@ add_chain_mfma_kernel(AddArgs A) {
         const int tiles = (nout + 31) >> 5;
         // s_{i+1}'s words from 32 up are carry_{i+1}'s (x_{i+1} < 32 words): tiles T >= 1 store
         // them (u32 words of the output limbs) below the output's capacity; bit i+1 does the rest
-        uint32_t *son = (uint32_t *)(po + offo);
+        // (its address made wave-uniform by hand: the tiles' stores take their base from SGPRs)
+        const uint64_t sonv = (uint64_t)(uintptr_t)(po + offo);
+        const uint64_t son = ((uint64_t)rfl((uint32_t)(sonv >> 32)) << 32) | rfl((uint32_t)sonv);
         const int capn = 2 * (int)cap_of(A.ob.b[i + 1]);
         const int wlo = 32;
-        // the top tile's whole window: words 32(tiles-1) - D .. + 32 + 2 NC
-        ring_fill<Cfg::kMirror>(C, ring, tab, 32 * (tiles - 1) - D, 32 + 2 * NC, lane);
         int ldeg = -1;
         // deg(P_i * carry_i) = deg P_i + deg carry_i exactly (GF(2)[X] has no zero divisors), so
         // when that is above deg ab_i it is carry_{i+1}'s degree; only otherwise (a short carry:
@@ -350,51 +345,87 @@ add_chain_mfma_kernel(AddArgs A) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) acc[j] = 8388608.0f;
         uint32_t gprev = 0u;
-        // window words 32T + col - D + h + 2c: one base slot, chunk c at +2c slots (32 B)
-        auto rbase = [&](int T) {
-            return (const uint4 *)&ring[((32 * T + col - D + h) & (kMfmaRingSlots - 1)) * 4];
-        };
+        // Per-lane LDS addresses of the tile loop (bytes; one VGPR per access pattern, opaque so
+        // that each stays one register updated by one add per tile):
+        //   rb0   the window of ring phase 0: slot col + h; tile T reads phase T % 4, chunk c at +2c
+        //         slots (32 B, immediates);
+        //   put0  lane pair 2j, 2j + 1 fills the halves of slot j of a phase;
+        //   cF    bytes 2 (l % 2), + 1 of the carry word 32(T-1) - D + l/2 staged for the next tile;
+        //   cW    the tile's output word 32T + col.
+        const uint32_t rb0 = lds_opaque(lds_addr(ring) + 16u * (uint32_t)(col + h));
+        const uint32_t put0 = lds_opaque(lds_addr(ring) + 8u * (uint32_t)lane);
+        uint32_t cF = lds_opaque(lds_addr(C) + 4u * (uint32_t)(32 * (tiles - 2) - D + (lane >> 1)) +
+                                 2u * (uint32_t)(lane & 1));
+        uint32_t cW = lds_opaque(lds_addr(C) + 4u * (uint32_t)(32 * (tiles - 1) + col));
+        const uint32_t col4 = 4u * (uint32_t)col; // the sum word's offset from the tile's base
+        auto rbase = [&](int T) { return rb0 + kPhaseBytes * (uint32_t)(T & 3); };
+        // The top tile's whole window, words 32(tiles-1) - D .. + 32 + 2 NC, as whole ring phases
+        // (tiles - 1 + p) % 4: the same byte reads, lookups and stores as a tile's side stages,
+        // the carry words at immediate offsets of cF (the words past the window are images of
+        // real carry words too, in slots no tile reads before it refills them)
+        {
+            constexpr int kPasses = (32 + 2 * NC + 31) / 32;
+            uint32_t f0[kPasses], f1[kPasses];
+#pragma unroll
+            for (int p = 0; p < kPasses; ++p) {
+                f0[p] = lds_at<const uint8_t>(cF)[128 * (p + 1)];
+                f1[p] = lds_at<const uint8_t>(cF)[128 * (p + 1) + 1];
+            }
+#pragma unroll
+            for (int p = 0; p < kPasses; ++p) f0[p] = tab[f0[p]], f1[p] = tab[f1[p]];
+#pragma unroll
+            for (int p = 0; p < kPasses; ++p) {
+                const uint32_t ph = kPhaseBytes * (uint32_t)((tiles - 1 + p) & 3);
+                const u32x2 fn = {f0[p], f1[p]};
+                *lds_at<u32x2>(put0 + ph) = fn;
+                if (ph < 16u * (uint32_t)Cfg::kMirror) *lds_at<u32x2>(put0 + ph + 16u * kMfmaRingSlots) = fn;
+            }
+        }
         wsync(); // the first tile's ring images are written
         constexpr int kPrefetch = kPrefetchOf<NC>;
-        uint4 pf[kPrefetch];
+        u32x4 pf[kPrefetch];
 #pragma unroll
-        for (int c = 0; c < kPrefetch; ++c) pf[c] = rbase(tiles - 1)[2 * c];
+        for (int c = 0; c < kPrefetch; ++c) pf[c] = lds_at<const u32x4>(rbase(tiles - 1))[2 * c];
         // (NC = 13: the window base carries over, this tile's is the previous tile's next)
-        const uint4 *rb = rbase(tiles - 1);
+        uint32_t rb = rbase(tiles - 1);
+        // ab_i's word of the tile's output: zero above ab_i's tiles (tiles 0 and 1 at most: ab_i <
+        // 64 words, host plan), so it is set once here and read only behind a wave-uniform branch
+        uint32_t abw = 0u;
         for (int T = tiles - 1; T >= 0; --T) {
             wsync(); // ring images of this tile's window are written
             if constexpr (NC > 16) rb = rbase(T); // (NC = 25: carried over, it spilled)
-            const uint4 *rbn = rbase(T - 1); // (T = 0: rbn reads are not used)
-            // the next tile's 32 new window words (old carry: below 32T; their ring slots are not
-            // in this tile's window), one per lane pair, staged between this tile's MFMAs
+            // the next tile's 32 new window words (old carry: below 32T; their ring slots, phase
+            // (T - 1) % 4, are not in this tile's window), one per lane pair, staged between this
+            // tile's MFMAs
             // (tile 0 stages words -32-D+col too: its ring slots are outside tile 0's window, C
             // reads below the halo stay inside the block's LDS, and the next bit refills its window
             // before reading it, so no per-tile test is needed)
-            // (lane pair 2j, 2j + 1: word j's two halves, contiguous stores as in ring_fill)
-            const int fh = HM_RING_PAIRS ? lane & 1 : h;
-            const int fw = 32 * (T - 1) - D + (HM_RING_PAIRS ? lane >> 1 : col);
-            uint32_t fv;
-            uint2 fn;
-            // ab_i's word of this tile's output, read before the MFMAs (ab_i < 64 words: host plan;
-            // a wave-uniform branch: tiles 0 and 1 at most)
-            const int W = 32 * T + col;
-            uint32_t abw = 0u;
-            if (32 * T < nab) {
+            const uint32_t ph = kPhaseBytes * (uint32_t)((T - 1) & 3); // (scalar)
+            const uint32_t rbn = rb0 + ph;                       // (T = 0: rbn reads are not used)
+            const uint32_t pp = put0 + ph;
+            const bool mirror = ph < 16u * (uint32_t)Cfg::kMirror; // wave-uniform
+            uint32_t f0, f1;
+            u32x2 fn;
+            if (32 * T < nab) { // (wave-uniform)
                 asm volatile("" ::: "memory");
+                const int W = 32 * T + (lane_opaque() & 31); // (built here: not a per-tile value)
                 abw = W < nab ? abi[W] : 0u;
             }
             __builtin_amdgcn_s_setprio(1); // the MFMA phase keeps the pipe
             acc = tile_mfma<NC>(Af, rb, rbn, pf, acc, [&](int stage) {
                 // (the empty asm keep each stage's arithmetic from being hoisted into an earlier
                 // stage, where it would wait for the read of the stage before)
-                if (stage == 0) fv = C[fw];
-                else if (stage == 1) {
-                    asm volatile("" : "+v"(fv));
-                    fv >>= 16 * fh;
-                    fn.x = tab[fv & 0xFFu], fn.y = tab[(fv >> 8) & 0xFFu];
+                if (stage == 0) {
+                    // two byte reads: each is a table index as it stands (one word read took a
+                    // shift and two field extracts to split)
+                    f0 = lds_at<const uint8_t>(cF)[0], f1 = lds_at<const uint8_t>(cF)[1];
+                } else if (stage == 1) {
+                    asm volatile("" : "+v"(f0), "+v"(f1));
+                    fn.x = tab[f0], fn.y = tab[f1];
                 } else {
-                    asm volatile("" : "+v"(fn.x), "+v"(fn.y));
-                    ring_put<Cfg::kMirror>(ring, fw, fh, fn);
+                    asm volatile("" : "+v"(fn));
+                    *lds_at<u32x2>(pp) = fn;
+                    if (mirror) *lds_at<u32x2>(pp + 16u * kMfmaRingSlots) = fn;
                 }
             });
             __builtin_amdgcn_s_setprio(0);
@@ -415,21 +446,29 @@ add_chain_mfma_kernel(AddArgs A) {
             const bool full = T >= 1 && 32 * T + 32 <= capn;
             young += full ? 1 : 0;
             if (h == 0) {
-                C[W] = v;
+                *lds_at<uint32_t>(cW) = v;
+                // the sum word goes out from a scalar base (the tile's first word, advanced on the
+                // scalar unit) plus the lane's constant 32-bit offset: no per-lane 64-bit address
+                // arithmetic.  (asm: the compiler folds the tile into a 64-bit VGPR address)
+                const uint64_t sT = son + 128u * (uint32_t)T;
                 if (full) {
-                    asm volatile("" ::: "memory");
-                    son[W] = v;
-                } else if (W >= wlo && W < capn) son[W] = v;
+                    sum_store(sT, col4, v);
+                } else {
+                    const int W = 32 * T + (lane_opaque() & 31);
+                    if (W >= wlo && W < capn) sum_store(sT, col4, v);
+                }
             }
             // a wave-uniform branch (the empty volatile asm keeps the compiler from if-converting
             // it into per-lane selects that run on every tile)
             if (track) {
                 asm volatile("" ::: "memory");
-                int Wq = W; // (opaque: its bit position is not strength-reduced into every tile)
-                asm volatile("" : "+v"(Wq));
+                // (opaque: its bit position is not strength-reduced into every tile)
+                const int Wq = 32 * T + (lane_opaque() & 31);
                 if (h == 0 && v) ldeg = max(ldeg, Wq * 32 + 31 - (int)__builtin_clz(v));
             }
             rb = rbn;
+            cF -= 128u;
+            cW -= 128u;
         }
         const int deg = track ? wave_max_i32(ldeg) : alg;
         nc = deg >= 0 ? (deg >> 5) + 1 : 0;

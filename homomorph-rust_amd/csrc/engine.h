@@ -451,7 +451,8 @@ template <int NC> struct MfmaCfg {
 #define HM_MIRROR13 32
 #endif
     // (a whole-ring mirror at NC = 13, whose two copies need no per-lane test, measured 0.5 %
-    // slower: 0.5764 against 0.5726 ms per step)
+    // slower: 0.5764 against 0.5726 ms per step; since then the ring's origin moves with the
+    // bit and the mirror test is wave-uniform, adder_mfma.hip "Ring slot")
     static constexpr int kMirror = NC <= 16 ? HM_MIRROR13 : 64;
     static constexpr int kRingWords = 4 * (kMfmaRingSlots + kMirror);
     static_assert(2 * NC - 1 <= kMirror, "ring mirror");

@@ -45,6 +45,21 @@ __device__ __forceinline__ int lane_opaque() {
     return l;
 }
 
+// LDS through 32-bit byte addresses: a hot loop keeps ONE address VGPR per access pattern and
+// reaches everything else by the DS instructions' immediate offsets.  An address passed through
+// lds_opaque() is a value the compiler cannot see into, so it does not fold a buffer's constant
+// offset into the immediates (where it overflows the 8-bit dword offsets of ds_read2_b32 and
+// costs one v_add per read) or rebuild the address from its parts on every use.
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+#define HM_LDS __attribute__((address_space(3)))
+__device__ __forceinline__ uint32_t lds_addr(const void *p) { return (uint32_t)(uintptr_t)p; }
+__device__ __forceinline__ uint32_t lds_opaque(uint32_t a) {
+    asm volatile("" : "+v"(a));
+    return a;
+}
+template <class T> __device__ __forceinline__ HM_LDS T *lds_at(uint32_t a) { return (HM_LDS T *)a; }
+
 // byte -> its 8 bits as fp4 nibbles (1.0 = 0b0010 per set bit); block-cooperative fill
 __device__ __forceinline__ void nibble_table(uint32_t *tab) {
     for (uint32_t k = threadIdx.x; k < 256; k += blockDim.x) {
