@@ -102,8 +102,32 @@ uint16_t min_d_over_delta(hm_op op) { // src/impls/numbers.rs:27-50
     case HM_OP_XOR: case HM_OP_NOT: return 1;
     case HM_OP_ADD: return 21;
     case HM_OP_MUL: case HM_OP_MUL_SIGNED: return 64;
+    default: break; // HM_OP_SUB .. HM_OP_GE depend on the width: borrow_min_d_over_delta
     }
     return 0xFFFF;
+}
+
+bool is_borrow_op(hm_op op) { return op >= HM_OP_SUB && op <= HM_OP_GE; }
+bool is_compare_op(hm_op op) { return op >= HM_OP_EQ && op <= HM_OP_GE; }
+bool is_ordering_op(hm_op op) { return op >= HM_OP_LT && op <= HM_OP_GE; }
+
+// 2m + 1 with m the borrow circuit's degree in fresh input bits: nbits + 1 for the orderings
+// (the borrow out of the top bit), nbits for subtraction and equality.  A fresh bit's noise has
+// degree delta + 1 <= 2 delta, so d >= (2m + 1) delta gives m (delta + 1) < d.
+uint16_t borrow_min_d_over_delta(hm_op op, uint32_t nbits) {
+    const uint32_t m = nbits + (is_ordering_op(op) ? 1u : 0u);
+    return (uint16_t)(2 * m + 1);
+}
+
+// Borrow bounds wb_0 = 0, wb_{i+1} = max(a_i + b_i, max(a_i, b_i) + wb_i) for i < upto; false
+// beyond the engine's degree range.  wb[i] for i <= upto.
+bool borrow_bounds(uint32_t upto, const uint32_t *a, const uint32_t *b, std::vector<int64_t> &wb) {
+    wb.assign(upto + 1, 0);
+    for (uint32_t i = 0; i < upto; ++i) {
+        wb[i + 1] = std::max<int64_t>((int64_t)a[i] + b[i], std::max<int64_t>(a[i], b[i]) + wb[i]);
+        if (wb[i + 1] >= (int64_t)1 << 30) return false;
+    }
+    return true;
 }
 
 // the bound of an output must cover the computed bound, bit by bit
@@ -574,8 +598,17 @@ hm_status hm_ctx_set_mul_products(hm_ctx *c, uint32_t products) try {
 } HM_ABI_CATCH
 
 hm_status hm_validate_operation(const hm_ctx *c, hm_op op, uint16_t *req) try {
-    if (!c) return HM_ERR_INVALID_ARGUMENT;
+    if (!c || is_borrow_op(op)) return HM_ERR_INVALID_ARGUMENT; // those need a width (_bits)
     const uint16_t m = min_d_over_delta(op);
+    if (req) *req = m;
+    if ((uint32_t)c->d < (uint32_t)m * (uint32_t)c->delta) return HM_ERR_INVALID_PARAMETERS;
+    return HM_OK;
+} HM_ABI_CATCH
+
+hm_status hm_validate_operation_bits(const hm_ctx *c, hm_op op, uint32_t nbits, uint16_t *req) try {
+    if (!is_borrow_op(op)) return hm_validate_operation(c, op, req);
+    if (!c || nbits == 0 || nbits > HM_MAX_BITS) return HM_ERR_INVALID_ARGUMENT;
+    const uint16_t m = borrow_min_d_over_delta(op, nbits);
     if (req) *req = m;
     if ((uint32_t)c->d < (uint32_t)m * (uint32_t)c->delta) return HM_ERR_INVALID_PARAMETERS;
     return HM_OK;
@@ -612,6 +645,37 @@ hm_status hm_add_out_bounds(uint32_t L, const uint32_t *a, const uint32_t *b, ui
             c = (c < 0) ? ab : std::max(ab, p + c);
         }
     }
+    return HM_OK;
+} HM_ABI_CATCH
+
+// Degree bounds of the ripple-borrow circuits.
+hm_status hm_sub_out_bounds(uint32_t L, const uint32_t *a, const uint32_t *b, uint32_t *out) try {
+    if (!a || !b || !out || L == 0 || L > HM_MAX_BITS) return HM_ERR_INVALID_ARGUMENT;
+    std::vector<int64_t> wb;
+    if (!borrow_bounds(L - 1, a, b, wb)) return HM_ERR_UNSUPPORTED;
+    for (uint32_t i = 0; i < L; ++i) {
+        const int64_t s = std::max<int64_t>(std::max(a[i], b[i]), wb[i]);
+        if (s >= (int64_t)1 << 30) return HM_ERR_UNSUPPORTED;
+        out[i] = (uint32_t)s;
+    }
+    return HM_OK;
+} HM_ABI_CATCH
+
+hm_status hm_compare_out_bounds(hm_op cmp, uint32_t L, const uint32_t *a, const uint32_t *b,
+                                uint32_t out[8]) try {
+    if (!a || !b || !out || L == 0 || L > HM_MAX_BITS || !is_compare_op(cmp))
+        return HM_ERR_INVALID_ARGUMENT;
+    int64_t r = 0;
+    if (is_ordering_op(cmp)) { // (the recurrence is symmetric: exchanging the operands keeps it)
+        std::vector<int64_t> wb;
+        if (!borrow_bounds(L, a, b, wb)) return HM_ERR_UNSUPPORTED;
+        r = wb[L];
+    } else {
+        for (uint32_t i = 0; i < L; ++i) r += std::max(a[i], b[i]);
+        if (r >= (int64_t)1 << 30) return HM_ERR_UNSUPPORTED;
+    }
+    out[0] = (uint32_t)r;
+    for (int k = 1; k < 8; ++k) out[k] = 0;
     return HM_OK;
 } HM_ABI_CATCH
 
@@ -983,6 +1047,76 @@ hm_status hm_gate_batch(hm_ctx *c, hm_op gate, const hm_batch *a, const hm_batch
     fill_bounds(G.ob, out);
     DeviceGuard g(c->device);
     return launch_gate(G, c->stream) ? hip_fail(c, hipGetLastError()) : HM_OK;
+} HM_ABI_CATCH
+
+// The ripple-borrow kernel over checked batches (a, b: L bits; out covers its bounds).  chain: the
+// degree bound of the last borrow (or equality prefix) the kernel forms.
+static hm_status borrow_run(hm_ctx *c, int mode, bool flip, bool sgn, const hm_batch *a,
+                            const hm_batch *b, hm_batch *out, int64_t chain) {
+    const uint32_t L = a->nbits;
+    uint32_t SA = 2, SB = 2;
+    for (uint32_t i = 0; i < L; ++i) {
+        SA = std::max(SA, 2 * cap_of(a->bound[i]));
+        SB = std::max(SB, 2 * cap_of(b->bound[i]));
+    }
+    const uint32_t SX = std::max(SA, SB);
+    BorrowArgs G{};
+    G.mode = mode, G.flip = flip, G.sgn = sgn;
+    // a_i | b_i | x_i | p_i | generate term a_i b_i + b_i | two borrow buffers: the widest
+    // product p_i w_i spans words(p_i) + words(w_i) <= SX + chain / 32 + 1 words
+    G.oA = 0, G.oB = SA + 2, G.oX = G.oB + SB + 2, G.oP = G.oX + SX + 2, G.oG = G.oP + SX + 2;
+    G.oW = G.oG + SA + SB + 2;
+    G.cw = SX + (uint32_t)(chain / 32) + 3;
+    G.lds_per_wave = G.oW + 2 * G.cw;
+    if ((size_t)G.lds_per_wave * 16 > 160 * 1024) return HM_ERR_UNSUPPORTED;
+    G.a = batch_arg(a), G.b = batch_arg(b), G.out = batch_arg(out);
+    G.n = a->n, G.nbits = L;
+    G.status = c->d_status;
+    fill_bounds(G.ab, a);
+    fill_bounds(G.bb, b);
+    fill_bounds(G.ob, out);
+    DeviceGuard g(c->device);
+    return launch_borrow(G, c->stream) ? hip_fail(c, hipGetLastError()) : HM_OK;
+}
+
+hm_status hm_sub_batch(hm_ctx *c, const hm_batch *a, const hm_batch *b, hm_batch *out) try {
+    if (!c || !a || !b || !out) return HM_ERR_INVALID_ARGUMENT;
+    if (hm_status st = check_batch(a); st) return st;
+    if (hm_status st = check_batch(b); st) return st;
+    if (hm_status st = check_batch(out); st) return st;
+    if (b->nbits != a->nbits || b->n != a->n || out->nbits != a->nbits || out->n != a->n)
+        return HM_ERR_INVALID_ARGUMENT;
+    const uint32_t L = a->nbits;
+    if (hm_status st = hm_validate_operation_bits(c, HM_OP_SUB, L, nullptr); st) return st;
+    std::vector<uint32_t> need(L);
+    if (hm_status st = hm_sub_out_bounds(L, a->bound, b->bound, need.data()); st) return st;
+    if (!covers(out, need)) return HM_ERR_INVALID_ARGUMENT;
+    if (a->n == 0) return HM_OK;
+    std::vector<int64_t> wb;
+    borrow_bounds(L - 1, a->bound, b->bound, wb);
+    return borrow_run(c, kBorrowSub, false, false, a, b, out, wb[L - 1]);
+} HM_ABI_CATCH
+
+hm_status hm_compare_batch(hm_ctx *c, hm_op cmp, const hm_batch *a, const hm_batch *b,
+                           int is_signed, hm_batch *out) try {
+    if (!c || !a || !b || !out || !is_compare_op(cmp)) return HM_ERR_INVALID_ARGUMENT;
+    if (hm_status st = check_batch(a); st) return st;
+    if (hm_status st = check_batch(b); st) return st;
+    if (hm_status st = check_batch(out); st) return st;
+    if (b->nbits != a->nbits || b->n != a->n || out->nbits != 8 || out->n != a->n)
+        return HM_ERR_INVALID_ARGUMENT;
+    const uint32_t L = a->nbits;
+    if (hm_status st = hm_validate_operation_bits(c, cmp, L, nullptr); st) return st;
+    std::vector<uint32_t> need(8);
+    if (hm_status st = hm_compare_out_bounds(cmp, L, a->bound, b->bound, need.data()); st)
+        return st;
+    if (!covers(out, need)) return HM_ERR_INVALID_ARGUMENT;
+    if (a->n == 0) return HM_OK;
+    if (cmp == HM_OP_GT || cmp == HM_OP_LE) std::swap(a, b); // a > b is b < a
+    const bool flip = cmp == HM_OP_NE || cmp == HM_OP_GE || cmp == HM_OP_LE;
+    const bool ord = is_ordering_op(cmp);
+    return borrow_run(c, ord ? kBorrowLt : kBorrowEq, flip, ord && is_signed != 0, a, b, out,
+                      need[0]);
 } HM_ABI_CATCH
 
 // ------------------------------------------------------------------ polynomial primitives

@@ -112,6 +112,26 @@ struct GateArgs {
     Bounds ab, bb, ob;
 };
 
+// Ripple-borrow chain (kernels.hip borrow_kernel): subtraction, the four orderings and equality,
+// one wavefront per value, everything in LDS.  The host exchanges the operands
+// for > and <=, so the kernel knows three chains and a constant:
+//   kBorrowSub  out_i = x_i + w_i, w_{i+1} = a_i b_i + b_i + p_i w_i   (x = a + b, p = x + 1)
+//   kBorrowLt   the same borrows through bit nbits - 1; the result is w_nbits (+ 1 when flip)
+//   kBorrowEq   e_{i+1} = p_i e_i from e_0 = 1; the result is e_nbits (+ 1 when flip)
+enum { kBorrowSub = 0, kBorrowLt = 1, kBorrowEq = 2 };
+struct BorrowArgs {
+    int mode;          // kBorrowSub / kBorrowLt / kBorrowEq
+    uint32_t flip;     // comparisons: the result plus the unit polynomial (>=, <=, !=)
+    uint32_t sgn;      // kBorrowLt on a signed type: bit nbits - 1 generates a_i b_i + a_i
+    BatchArg a, b, out;
+    uint64_t n;
+    uint32_t nbits;    // input bits (a comparison's output has 8)
+    uint32_t lds_per_wave, oA, oB, oX, oP, oG, oW; // word offsets in a wave's LDS slice
+    uint32_t cw;       // words of each of the two borrow buffers at oW
+    int *status;
+    Bounds ab, bb, ob;
+};
+
 // Column-parallel carry-save multiplier (mul_engine.hip, mul_host.cpp).  Column i of
 // mul_unsigned_internal (common.rs:66-105) XORs its items x_0..x_{n-1} (the partial products
 // a_j b_{i-j}, then the previous column's carries) into result_i and pushes the carry
@@ -389,6 +409,7 @@ int launch_add_chain_valu(const AddArgs &a, void *stream);
 int launch_encrypt(const EncArgs &a, void *stream);
 int launch_decrypt(const DecArgs &a, void *stream);
 int launch_gate(const GateArgs &a, void *stream);
+int launch_borrow(const BorrowArgs &a, void *stream);
 int launch_mul_stage(const MulStageArgs &a, void *stream);
 int launch_mul_pp(const MulPPArgs &a, void *stream);
 int launch_mul_scan(const MulScanArgs &a, void *stream);

@@ -1,5 +1,7 @@
 // kernels.hip — gfx950 kernels of the gates and the single-polynomial primitives:
 //   gate_kernel     elementwise AND/OR/XOR/NOT (common.rs:5-35)
+//   borrow_kernel   subtraction, ==, !=, <, <=, >, >= as one ripple-borrow chain (no reference
+//                   circuit: DESIGN.md s4.4a)
 //   poly_* kernels  single-polynomial primitives for unit parity (polynomial.rs:190-365)
 // (adder: adder.hip; cipher: cipher.hip; carry-save multiplier: mul_engine.hip)
 #include <hip/hip_runtime.h>
@@ -61,6 +63,97 @@ int launch_gate(const GateArgs &g, void *stream) {
     const uint64_t blocks = (g.n + wpb - 1) / wpb;
     if (blocks == 0) return 0;
     hipLaunchKernelGGL(gate_kernel, dim3((unsigned)blocks), dim3(64 * wpb),
+                       (size_t)g.lds_per_wave * 4 * wpb, (hipStream_t)stream, g);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Ripple-borrow chain: subtraction, orderings and equality (BorrowArgs).  One
+// wavefront per value, bit by bit through LDS like the gates; the borrow lives in two ping-pong
+// buffers because wave_mul's Dst may not alias its operands.
+
+// X = A ^ B and P = X ^ 1 (x_i = a_i + b_i, p_i = x_i + 1); their word counts (0 = null).
+__device__ __forceinline__ void xor_and_not(const uint32_t *A, int na, const uint32_t *B, int nb,
+                                            uint32_t *X, uint32_t *P, int *nx, int *np) {
+    const int n = max(max(na, nb), 1);
+    int ldx = -1, ldp = -1;
+    for (int w = lane_id(); w < n; w += kWave) {
+        const uint32_t v = (w < na ? A[w] : 0u) ^ (w < nb ? B[w] : 0u);
+        const uint32_t p = v ^ (w == 0 ? 1u : 0u);
+        X[w] = v;
+        P[w] = p;
+        if (v) ldx = w * 32 + 31 - __builtin_clz(v);
+        if (p) ldp = w * 32 + 31 - __builtin_clz(p);
+    }
+    *nx = words_of(wave_max_i32(ldx));
+    *np = words_of(wave_max_i32(ldp));
+}
+
+__global__ void __launch_bounds__(256) borrow_kernel(BorrowArgs G) {
+    extern __shared__ uint32_t lds[];
+    const int wave = (int)rfl(threadIdx.x >> 6); // wave-uniform by construction
+    const uint64_t e = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave;
+    if (e >= G.n) return;
+    const int lane = lane_id();
+    uint32_t *L = lds + (size_t)wave * G.lds_per_wave;
+    uint32_t *Ab = L + G.oA, *Bb = L + G.oB, *X = L + G.oX, *P = L + G.oP, *Gt = L + G.oG;
+    uint32_t *W = L + G.oW, *Wn = W + G.cw;
+    const uint64_t *pa = G.a.limbs + e * G.a.stride;
+    const uint64_t *pb = G.b.limbs + e * G.b.stride;
+    uint64_t *po = G.out.limbs + e * G.out.stride;
+    uint32_t offa = 0, offb = 0, offo = 0;
+    int nw = 0; // w_0 = 0
+    if (G.mode == kBorrowEq) { // e_0 = 1
+        if (lane == 0) W[0] = 1u;
+        nw = 1;
+    }
+    for (uint32_t i = 0; i < G.nbits; ++i) {
+        const int na = load_bit(pa + offa, rfl(G.a.degree[e * G.nbits + i]), G.ab.b[i], Ab, G.status);
+        const int nb = load_bit(pb + offb, rfl(G.b.degree[e * G.nbits + i]), G.bb.b[i], Bb, G.status);
+        wsync();
+        int nx, np, nout;
+        xor_and_not(Ab, na, Bb, nb, X, P, &nx, &np);
+        wsync();
+        if (G.mode == kBorrowSub) {
+            store_xor_bit(X, nx, W, nw, po + offo, G.ob.b[i], G.out.degree + e * G.nbits + i,
+                          G.status);
+            offo += cap_of(G.ob.b[i]);
+            if (i + 1 == G.nbits) break; // the last borrow is not needed
+        }
+        int ng = 0;
+        if (G.mode != kBorrowEq) {
+            // generate: a_i b_i + b_i (not a and b); the signed top bit has the operands' roles
+            // exchanged, a_i b_i + a_i
+            const bool top = G.sgn && i + 1 == G.nbits;
+            ng = words_of(wave_mul<kQSmall, 8>(Ab, na, Bb, nb, top ? Ab : Bb, top ? na : nb, Gt,
+                                               &nout));
+            wsync();
+        }
+        nw = words_of(wave_mul<kQSmall, 8>(P, np, W, nw, Gt, ng, Wn, &nout));
+        wsync();
+        uint32_t *t = W;
+        W = Wn, Wn = t;
+        offa += cap_of(G.ab.b[i]);
+        offb += cap_of(G.bb.b[i]);
+    }
+    if (G.mode == kBorrowSub) return;
+    // Ciphered<bool>: bit 0 is the result (plus 1 for >=, <=, !=), bits 1..7 are null
+    if (lane == 0) X[0] = 1u;
+    wsync();
+    store_xor_bit(W, nw, X, G.flip ? 1 : 0, po, G.ob.b[0], G.out.degree + e * 8, G.status);
+    offo = cap_of(G.ob.b[0]);
+    for (uint32_t k = 1; k < 8; ++k) {
+        store_xor_bit(nullptr, 0, nullptr, 0, po + offo, G.ob.b[k], G.out.degree + e * 8 + k,
+                      G.status);
+        offo += cap_of(G.ob.b[k]);
+    }
+}
+
+int launch_borrow(const BorrowArgs &g, void *stream) {
+    const int wpb = 4;
+    const uint64_t blocks = (g.n + wpb - 1) / wpb;
+    if (blocks == 0) return 0;
+    hipLaunchKernelGGL(borrow_kernel, dim3((unsigned)blocks), dim3(64 * wpb),
                        (size_t)g.lds_per_wave * 4 * wpb, (hipStream_t)stream, g);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -29,9 +29,12 @@ __all__ = [
     "Parameters", "SecretKey", "PublicKey", "Context", "Ciphered", "Polys",
     "HomomorphicAndGate", "HomomorphicOrGate", "HomomorphicXorGate", "HomomorphicNotGate",
     "HomomorphicAddition", "HomomorphicMultiplication",
+    "HomomorphicSubtraction", "HomomorphicEqual", "HomomorphicNotEqual", "HomomorphicLessThan",
+    "HomomorphicLessEqual", "HomomorphicGreaterThan", "HomomorphicGreaterEqual",
     "OperationError", "ContextCryptoError", "CipherError", "EngineError", "LibraryMissing",
     "EngineGraph",
-    "add_out_bounds", "mul_out_bounds", "gate_out_bounds", "batch_stride", "caps",
+    "add_out_bounds", "mul_out_bounds", "gate_out_bounds", "sub_out_bounds",
+    "compare_out_bounds", "batch_stride", "caps",
 ]
 
 
@@ -105,6 +108,58 @@ class HomomorphicAddition(_Op):
 
 class HomomorphicMultiplication(_Op):
     MIN_D_OVER_DELTA, CODE = 64, _lib.OP_MUL
+
+
+class _BorrowOp(_Op):
+    """The engine's ripple-borrow operations (no reference circuit).  Their
+    requirement depends on the width of the type: 2m + 1 with m the circuit's degree in fresh
+    input bits (EXTRA_DEGREE more than the width)."""
+    MIN_D_OVER_DELTA = None
+    EXTRA_DEGREE = 0
+
+    @classmethod
+    def min_d_over_delta(cls, nbits: int) -> int:
+        return 2 * (int(nbits) + cls.EXTRA_DEGREE) + 1
+
+
+class HomomorphicSubtraction(_BorrowOp):
+    CODE = _lib.OP_SUB
+
+
+class _Compare(_BorrowOp):
+    """A comparison: the result is a batch of Ciphered<bool> (8 ciphertext bits)."""
+
+
+class HomomorphicEqual(_Compare):
+    CODE = _lib.OP_EQ
+
+
+class HomomorphicNotEqual(_Compare):
+    CODE = _lib.OP_NE
+
+
+class HomomorphicLessThan(_Compare):
+    CODE, EXTRA_DEGREE = _lib.OP_LT, 1
+
+
+class HomomorphicLessEqual(_Compare):
+    CODE, EXTRA_DEGREE = _lib.OP_LE, 1
+
+
+class HomomorphicGreaterThan(_Compare):
+    CODE, EXTRA_DEGREE = _lib.OP_GT, 1
+
+
+class HomomorphicGreaterEqual(_Compare):
+    CODE, EXTRA_DEGREE = _lib.OP_GE, 1
+
+
+def _is_borrow(op) -> bool:
+    return isinstance(op, type) and issubclass(op, _BorrowOp)
+
+
+def _is_compare(op) -> bool:
+    return isinstance(op, type) and issubclass(op, _Compare)
 
 
 # ------------------------------------------------------------------ parameters / keys
@@ -207,6 +262,23 @@ def mul_out_bounds(a_bound, b_bound, signed=False) -> np.ndarray:
     out = np.zeros_like(a)
     _check(lib().hm_mul_out_bounds(a.size, _p32(a), _p32(b), int(signed), _p32(out)),
            "hm_mul_out_bounds")
+    return out
+
+
+def sub_out_bounds(a_bound, b_bound) -> np.ndarray:
+    """hm_sub_out_bounds: per-bit bounds of a - b (ripple-borrow circuit)."""
+    a, b = _u32(a_bound), _u32(b_bound)
+    out = np.zeros_like(a)
+    _check(lib().hm_sub_out_bounds(a.size, _p32(a), _p32(b), _p32(out)), "hm_sub_out_bounds")
+    return out
+
+
+def compare_out_bounds(op, a_bound, b_bound) -> np.ndarray:
+    """hm_compare_out_bounds: the 8 bounds of a comparison's Ciphered<bool> (bits 1..7 null)."""
+    a, b = _u32(a_bound), _u32(b_bound)
+    out = np.zeros(8, dtype=np.uint32)
+    _check(lib().hm_compare_out_bounds(op.CODE, a.size, _p32(a), _p32(b), _p32(out)),
+           "hm_compare_out_bounds")
     return out
 
 
@@ -632,21 +704,30 @@ class Context:
         return raw.view(dt.newbyteorder("<")).reshape(c.n).astype(dt)
 
     # ---- operations (Context::apply1 / apply2, src/context.rs:496-527)
-    def validate_operation(self, op) -> None:
+    def validate_operation(self, op, nbits=None) -> None:
         """Context::validate_operation (src/context.rs:310-323).  Built-in operations ask the
-        engine (hm_validate_operation); a user operation supplies MIN_D_OVER_DELTA itself."""
+        engine (hm_validate_operation); a user operation supplies MIN_D_OVER_DELTA itself.
+        Subtraction and the comparisons need the width of the type (nbits): their requirement
+        grows with it (hm_validate_operation_bits)."""
         if not hasattr(op, "CODE"):
             req = int(op.MIN_D_OVER_DELTA)
             if self._params.d < req * self._params.delta:
                 raise OperationError(req, self._params.d, self._params.delta)
             return
         req = ctypes.c_uint16()
-        st = lib().hm_validate_operation(self._h, op.CODE, ctypes.byref(req))
+        if _is_borrow(op):
+            if nbits is None:
+                raise ValueError(f"{op.__name__} is validated for a width: pass nbits")
+            st = lib().hm_validate_operation_bits(self._h, op.CODE, int(nbits), ctypes.byref(req))
+        else:
+            st = lib().hm_validate_operation(self._h, op.CODE, ctypes.byref(req))
         if st == _lib.ERR_INVALID_PARAMETERS:
             raise OperationError(req.value, self._params.d, self._params.delta)
         _check(st, "validate_operation")
 
     def apply2(self, op, a: Ciphered, b: Ciphered, out_bound=None, signed=None) -> Ciphered:
+        if _is_borrow(op):
+            return self._apply_borrow(op, a, b, out_bound, signed)
         self.validate_operation(op)
         if op is HomomorphicAddition:
             need = add_out_bounds(a.bound, b.bound)
@@ -669,6 +750,20 @@ class Context:
             fn = lambda: lib().hm_gate_batch(self._h, op.CODE, ctypes.byref(ca),  # noqa
                                              ctypes.byref(cb), ctypes.byref(co))
         self._launch(fn, op.__name__)
+        return out
+
+    def _apply_borrow(self, op, a: Ciphered, b: Ciphered, out_bound, signed) -> Ciphered:
+        self.validate_operation(op, a.nbits)
+        if _is_compare(op):
+            need = compare_out_bounds(op, a.bound, b.bound)
+            out = Ciphered.empty(a.n, need if out_bound is None else out_bound, self.device,
+                                 np.dtype(np.bool_))
+            compare_into(self, op, a, b, out, signed)
+        else:
+            need = sub_out_bounds(a.bound, b.bound)
+            out = Ciphered.empty(a.n, need if out_bound is None else out_bound, self.device,
+                                 a.plain_dtype)
+            sub_into(self, a, b, out)
         return out
 
     def mul_plan_work(self, a_bound, b_bound, k=None, signed=False) -> float:
@@ -774,6 +869,24 @@ def mul_into(ctx: Context, a: Ciphered, b: Ciphered, out: Ciphered, signed=False
     ca, cb, co = a._c(), b._c(), out._c()
     ctx._launch(lambda: lib().hm_mul_batch(ctx._h, ctypes.byref(ca), ctypes.byref(cb),
                                            int(signed), ctypes.byref(co)), "hm_mul_batch")
+
+
+def sub_into(ctx: Context, a: Ciphered, b: Ciphered, out: Ciphered) -> None:
+    """hm_sub_batch into a preallocated output (bounds: sub_out_bounds)."""
+    ca, cb, co = a._c(), b._c(), out._c()
+    ctx._launch(lambda: lib().hm_sub_batch(ctx._h, ctypes.byref(ca), ctypes.byref(cb),
+                                           ctypes.byref(co)), "hm_sub_batch")
+
+
+def compare_into(ctx: Context, op, a: Ciphered, b: Ciphered, out: Ciphered, signed=None) -> None:
+    """hm_compare_batch into a preallocated 8-bit output (bounds: compare_out_bounds).  signed
+    defaults from a's plaintext dtype, as for multiplication; == and != ignore it."""
+    if signed is None:
+        signed = a.plain_dtype is not None and np.issubdtype(a.plain_dtype, np.signedinteger)
+    ca, cb, co = a._c(), b._c(), out._c()
+    ctx._launch(lambda: lib().hm_compare_batch(ctx._h, op.CODE, ctypes.byref(ca), ctypes.byref(cb),
+                                               int(bool(signed)), ctypes.byref(co)),
+                "hm_compare_batch")
 
 
 def mul_low_into(ctx: Context, a: Ciphered, b: Ciphered, k: int, out: Ciphered) -> None:

@@ -33,6 +33,7 @@ ERR_INTERNAL = 14
 
 # hm_op
 OP_AND, OP_OR, OP_XOR, OP_NOT, OP_ADD, OP_MUL, OP_MUL_SIGNED = range(7)
+OP_SUB, OP_EQ, OP_NE, OP_LT, OP_LE, OP_GT, OP_GE = range(7, 14)
 
 u64p = ctypes.POINTER(ctypes.c_uint64)
 u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -72,6 +73,7 @@ SIGNATURES = {
                                              ctypes.POINTER(ctypes.c_size_t)]),
     "hm_ctx_get_public_key": (ctypes.c_int, [vp, u64p, ctypes.c_size_t, u32p, u32p]),
     "hm_validate_operation": (ctypes.c_int, [vp, ctypes.c_int, u16p]),
+    "hm_validate_operation_bits": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_uint32, u16p]),
     "hm_ctx_set_mul_options": (ctypes.c_int, [vp, ctypes.c_uint32, ctypes.c_uint32]),
     "hm_ctx_set_mul_scratch": (ctypes.c_int, [vp, ctypes.c_uint64]),
     "hm_ctx_set_add_options": (ctypes.c_int, [vp, ctypes.c_uint32]),
@@ -98,6 +100,12 @@ SIGNATURES = {
     "hm_mul_low_batch": (ctypes.c_int, [vp, ctypes.POINTER(HmBatch), ctypes.POINTER(HmBatch),
                                         ctypes.c_uint32, ctypes.POINTER(HmBatch)]),
     "hm_gate_batch": (ctypes.c_int, [vp, ctypes.c_int] + [ctypes.POINTER(HmBatch)] * 3),
+    "hm_sub_out_bounds": (ctypes.c_int, [ctypes.c_uint32, u32p, u32p, u32p]),
+    "hm_compare_out_bounds": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, u32p, u32p, u32p]),
+    "hm_sub_batch": (ctypes.c_int, [vp] + [ctypes.POINTER(HmBatch)] * 3),
+    "hm_compare_batch": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(HmBatch),
+                                        ctypes.POINTER(HmBatch), ctypes.c_int,
+                                        ctypes.POINTER(HmBatch)]),
     "hm_poly_add_batch": (ctypes.c_int, [vp] + [ctypes.POINTER(HmPolys)] * 3),
     "hm_poly_mul_batch": (ctypes.c_int, [vp] + [ctypes.POINTER(HmPolys)] * 3),
     "hm_poly_rem_batch": (ctypes.c_int, [vp, ctypes.POINTER(HmPolys), u64p, ctypes.c_size_t,

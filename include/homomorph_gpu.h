@@ -34,8 +34,10 @@
 extern "C" {
 #endif
 
-#define HM_ABI_VERSION 5 /* 4: kernel timing by device stamps (HM_TIME_*), hm_ctx_last_hip_error;
-                            5: hm_ctx_clear_kernel_timing, hm_ctx_set_mul_scratch */
+#define HM_ABI_VERSION 6 /* 4: kernel timing by device stamps (HM_TIME_*), hm_ctx_last_hip_error;
+                            5: hm_ctx_clear_kernel_timing, hm_ctx_set_mul_scratch;
+                            6: HM_OP_SUB .. HM_OP_GE, hm_sub_batch, hm_compare_batch, their bounds,
+                               hm_validate_operation_bits */
 #define HM_MAX_BITS 128 /* u128 is the widest type with impls (src/impls/numbers/uint.rs:58) */
 
 typedef enum hm_status {
@@ -77,6 +79,17 @@ typedef enum hm_op {
     HM_OP_ADD = 4,            /* HomomorphicAddition,       min d/delta 21 */
     HM_OP_MUL = 5,            /* HomomorphicMultiplication, min d/delta 64 (unsigned types) */
     HM_OP_MUL_SIGNED = 6,     /* HomomorphicMultiplication on i8..i128 (common.rs:115-163) */
+    /* The engine's own operations (the reference defines no circuit for them): one ripple-borrow
+     * chain w_{i+1} = a_i b_i + b_i + (a_i + b_i + 1) w_i, w_0 = 0.  Their requirement depends on
+     * the width n of the type: min d/delta = 2m + 1 with m the circuit's degree in fresh input
+     * bits, m = n for SUB / EQ / NE and m = n + 1 for the orderings (hm_validate_operation_bits). */
+    HM_OP_SUB = 7,            /* HomomorphicSubtraction: a - b (wrapping), signed or unsigned */
+    HM_OP_EQ = 8,             /* HomomorphicEqual            a == b */
+    HM_OP_NE = 9,             /* HomomorphicNotEqual         a != b */
+    HM_OP_LT = 10,            /* HomomorphicLessThan         a <  b */
+    HM_OP_LE = 11,            /* HomomorphicLessEqual        a <= b */
+    HM_OP_GT = 12,            /* HomomorphicGreaterThan      a >  b */
+    HM_OP_GE = 13,            /* HomomorphicGreaterEqual     a >= b */
 } hm_op;
 
 typedef struct hm_ctx hm_ctx;
@@ -225,6 +238,14 @@ hm_status hm_ctx_kernel_timing(hm_ctx *ctx, double *total_ms, uint32_t *launches
 /* Context::validate_operation (src/context.rs:310-323): HM_OK or HM_ERR_INVALID_PARAMETERS with
  * the OperationError payload written to *required_min_d_over_delta (may be NULL). */
 hm_status hm_validate_operation(const hm_ctx *ctx, hm_op op, uint16_t *required_min_d_over_delta);
+/* The same for an operation on nbits-bit values.  HM_OP_AND .. HM_OP_MUL_SIGNED: exactly
+ * hm_validate_operation (nbits is not looked at).  HM_OP_SUB .. HM_OP_GE: the requirement
+ * 2m + 1 above (u32: 65 for SUB / EQ / NE, 67 for the orderings), which gives m (delta + 1) < d,
+ * so results on fresh inputs decrypt exactly; nbits outside 1..HM_MAX_BITS is
+ * HM_ERR_INVALID_ARGUMENT.  hm_validate_operation itself has no width: it returns
+ * HM_ERR_INVALID_ARGUMENT for HM_OP_SUB .. HM_OP_GE. */
+hm_status hm_validate_operation_bits(const hm_ctx *ctx, hm_op op, uint32_t nbits,
+                                     uint16_t *required_min_d_over_delta);
 
 /* Static degree bounds (host only, no device work).  fresh bound = max(d + dp, max deg T_i):
  * a subset sum of public-key rows plus the plaintext bit (cipher.rs:99-115). */
@@ -261,6 +282,17 @@ hm_status hm_mul_plan_work(hm_ctx *ctx, uint32_t nbits, uint32_t k, const uint32
 /* Output bounds of a gate (common.rs:5-35). */
 hm_status hm_gate_out_bounds(hm_op gate, uint32_t nbits, const uint32_t *a_bound,
                              const uint32_t *b_bound, uint32_t *out_bound);
+/* Output bounds of the ripple-borrow subtraction: with wb_0 = 0 and
+ * wb_{i+1} = max(a_i + b_i, max(a_i, b_i) + wb_i), bit 0 has bound max(a_0, b_0) and bit i
+ * max(a_i, b_i, wb_i).  (u32 at d + dp = 256: 2144 limbs per value.) */
+hm_status hm_sub_out_bounds(uint32_t nbits, const uint32_t *a_bound, const uint32_t *b_bound,
+                            uint32_t *out_bound);
+/* Output bounds of a comparison cmp = HM_OP_EQ .. HM_OP_GE (anything else is
+ * HM_ERR_INVALID_ARGUMENT) of nbits-bit values: a Ciphered<bool> of 8 ciphertext bits (bincode
+ * stores a bool as one byte).  out_bound[0] = wb_nbits for the orderings and sum max(a_i, b_i) for
+ * EQ / NE; out_bound[1..7] = 0 (null polynomials). */
+hm_status hm_compare_out_bounds(hm_op cmp, uint32_t nbits, const uint32_t *a_bound,
+                                const uint32_t *b_bound, uint32_t out_bound[8]);
 /* stride (limbs per value) of a batch with these bounds */
 uint64_t hm_batch_stride(uint32_t nbits, const uint32_t *bound);
 
@@ -306,6 +338,20 @@ hm_status hm_mul_low_batch(hm_ctx *ctx, const hm_batch *a, const hm_batch *b, ui
  * uint.rs:8-58).  For HM_OP_NOT, b is ignored (may be NULL). */
 hm_status hm_gate_batch(hm_ctx *ctx, hm_op gate, const hm_batch *a, const hm_batch *b,
                         hm_batch *out);
+
+/* a - b per value (wrapping; one circuit for signed and unsigned types): out_i = a_i + b_i + w_i
+ * over the borrow chain of HM_OP_SUB above.  Validates HM_OP_SUB at a->nbits.  a, b, out: same
+ * nbits and n; out bounds from hm_sub_out_bounds; out may not overlap a or b.  One launch, no
+ * workspace; HM_ERR_UNSUPPORTED when a value's chain does not fit a wavefront's share of LDS. */
+hm_status hm_sub_batch(hm_ctx *ctx, const hm_batch *a, const hm_batch *b, hm_batch *out);
+/* a cmp b per value, cmp = HM_OP_EQ .. HM_OP_GE.  Orderings: a < b is the borrow out of the top
+ * bit, w_nbits (is_signed: bit nbits - 1 generates a_i b_i + a_i, the sign bits' roles
+ * exchanged); > exchanges the operands; >= and <= add the unit polynomial.  Equality: the product
+ * of all a_i + b_i + 1 (is_signed is ignored).  out: a Ciphered<bool> batch, out->nbits == 8,
+ * bounds from hm_compare_out_bounds: bit 0 is the result, bits 1..7 are null polynomials.
+ * Validates cmp at a->nbits; otherwise as hm_sub_batch. */
+hm_status hm_compare_batch(hm_ctx *ctx, hm_op cmp, const hm_batch *a, const hm_batch *b,
+                           int is_signed, hm_batch *out);
 
 /* ---------------- polynomial primitives (src/polynomial.rs), for unit parity ---------------- */
 /* Polynomial::add (polynomial.rs:190-213) per pair: out = a ^ b, exact degree. */
