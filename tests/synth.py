@@ -1,0 +1,559 @@
+"""Synthetic operand batches that FILL their static bounds, the case table of the full-bounds tier
+and its references.  Shared by test_synth_reference.py (CPU: the references pinned
+against the C oracle, every path assertion) and test_gpu_full_bounds.py (GPU: the engine against
+the same references, bit-exact).
+
+A genuine fresh ciphertext bit has degree at most d + d', whatever `bound` its batch was allocated
+with, so everything the host derives from the bounds (LDS slices, workspace slots, tile widths,
+chunk counts, plan selection) only ever met data as long as its slot at the uniform fresh bounds.
+Here a polynomial "fills its bound" when its degree EQUALS the bound (kind FULL, MONO, ONES,
+SPARSE): the operand then occupies every word the host sized for it.  The other kinds put degrees
+at word and limb edges and the null / unit polynomials at every bit position.
+
+A polynomial is a Python int (bit k = coefficient of X^k), a value the list of its bit
+polynomials, least significant first (the model form of oracle/gf2_model.py).
+"""
+from __future__ import annotations
+
+import functools
+
+import numpy as np
+
+import borrow_model as bm
+from oracle import gf2_model as model
+
+KINDS = ("FULL", "MONO", "ONES", "NULL", "UNIT", "EDGE", "SPARSE", "LOW")
+PARAMS = (64, 64, 1, 64)      # satisfies every operation's d / delta here
+DEC_PARAMS = (128, 128, 1, 128)  # the decryption cases' secret key
+SEED = 4242
+
+
+# ------------------------------------------------------------------ polynomials
+def _rand_bits(rng, nbits):
+    """A uniformly random integer below 2^nbits."""
+    if nbits <= 0:
+        return 0
+    return int.from_bytes(rng.bytes((nbits + 7) // 8), "little") & ((1 << nbits) - 1)
+
+
+def _exact(rng, deg):
+    """Exact degree deg, random below it."""
+    return (1 << deg) | _rand_bits(rng, deg)
+
+
+def edge_degrees(bound):
+    b = int(bound)
+    return sorted({d for d in (31, 32, 33, 63, 64, 65, b - 1, 64 * (b // 64) - 1, 64 * (b // 64))
+                   if 0 <= d <= b})
+
+
+def poly(kind, bound, rng):
+    """One polynomial of the kind, valid for a bit of this bound (degree <= bound)."""
+    b = int(bound)
+    if kind == "FULL":
+        return _exact(rng, b)
+    if kind == "MONO":
+        return 1 << b
+    if kind == "ONES":
+        return (1 << (b + 1)) - 1
+    if kind == "NULL":
+        return 0
+    if kind == "UNIT":
+        return 1
+    if kind == "EDGE":
+        e = edge_degrees(b)
+        return _exact(rng, e[int(rng.integers(len(e)))])
+    if kind == "SPARSE":
+        p = 1 << b
+        for _ in range(2):
+            if b:
+                p |= 1 << int(rng.integers(b))
+        return p
+    if kind == "LOW":
+        return _exact(rng, int(rng.integers(b // 2)) if b >= 2 else 0)
+    raise KeyError(kind)
+
+
+def kind_of(e, i, shift=0):
+    """The scheduled kind of value e < 8, bit i."""
+    return KINDS[(e + i + shift) % 8]
+
+
+def operands(bound, n, seed, shift=0):
+    """n values over the per-bit bounds.  Value e < 8, bit i is of kind (e + i + shift) mod 8, so
+    every kind meets every bit position (the two operands of an operation take different shifts);
+    later values draw their kinds at random, FULL weighted highest."""
+    bound = np.asarray(bound, dtype=np.uint32)
+    rng = np.random.default_rng(seed)
+    weights = np.array([9.0] + [1.0] * 7) / 16.0
+    out = []
+    for e in range(n):
+        bits = []
+        for i, b in enumerate(bound):
+            k = kind_of(e, i, shift) if e < 8 else KINDS[int(rng.choice(8, p=weights))]
+            bits.append(poly(k, b, rng))
+        out.append(bits)
+    return out
+
+
+def full_pair(ba, bb, n, seed):
+    """(A, B): every a_i FULL (degree ba_i), every b_i of degree bb_i - 1 exactly.  With ba = bb
+    = B this is the pair that maximises deg P_i = deg x_i + deg a_i b_i = 3B - 1: equal tops would
+    cancel in x_i.  In every second value b_0 is FULL as well, so that the first carry or borrow
+    a_0 b_0 (+ b_0) has its full degree ba_0 + bb_0 and the chain after it stays as long as the
+    bounds allow."""
+    rng = np.random.default_rng(seed)
+    A = [[_exact(rng, int(b)) for b in ba] for _ in range(n)]
+    B = [[_exact(rng, max(int(b) - 1, 0)) for b in bb] for _ in range(n)]
+    for e in range(1, n, 2):
+        B[e][0] = _exact(rng, int(bb[0]))
+    return A, B
+
+
+def batch(ba, bb, nsched, npair, seed):
+    """nsched scheduled / random values followed by npair FULL / bound - 1 pairs."""
+    A = operands(ba, nsched, seed, 0)
+    B = operands(bb, nsched, seed + 1, 3)
+    PA, PB = full_pair(ba, bb, npair, seed + 2)
+    return A + PA, B + PB
+
+
+def words(p):
+    """32-bit words of a polynomial (0 for the null polynomial), as load_bit counts them."""
+    return (int(p).bit_length() + 31) // 32
+
+
+def u32(x):
+    return np.asarray(x, dtype=np.uint32)
+
+
+def uniform(nbits, b):
+    return np.full(nbits, b, dtype=np.uint32)
+
+
+# ------------------------------------------------------------------ bounds, restated
+def gate_bounds(op, ba, bb):
+    ba, bb = u32(ba).astype(np.int64), u32(bb).astype(np.int64)
+    if op in ("and", "or"):
+        return u32(ba + bb)
+    return u32(np.maximum(ba, bb)) if op == "xor" else u32(ba)
+
+
+def add_bounds(ba, bb):
+    out, c = [], -1
+    for i, (a, b) in enumerate(zip(map(int, ba), map(int, bb))):
+        x = max(a, b)
+        out.append(max(x, c))
+        ab = a + b
+        c = ab if c < 0 else max(ab, x + ab + c)
+    return u32(out)
+
+
+def mul_bounds(ba, bb):
+    """Carry-save array (common.rs:66-105) over bounds: a column's items are its partial products
+    then the carries of the column before; every item after the first sends on a carry."""
+    K = len(ba)
+    prev, res = [], []
+    for i in range(K):
+        items = [int(ba[j]) + int(bb[i - j]) for j in range(i + 1)] + prev
+        cur, pb = [], -1
+        for x in items:
+            if i + 1 < K and pb >= 0:
+                cur.append(pb + x)
+            pb = max(pb, x)
+        res.append(max(pb, 0))
+        prev = cur
+    return u32(res)
+
+
+def add_plan(ba, bb):
+    """hm_add_batch's sizing (capi.cpp), restated: cntX, maxPw, SC and what follows from them."""
+    wob = lambda b: 0 if b < 0 else b // 32 + 1  # noqa: E731  words_of_bound
+    L = len(ba)
+    cntX, SC, maxPw, cntAB, cb = 1, 2, 0, 1, -1
+    for i in range(L):
+        a, b = int(ba[i]), int(bb[i])
+        cntX = max(cntX, wob(max(a, b)))
+        if i + 1 < L:
+            x, ab = max(a, b), a + b
+            p = x + ab
+            cntAB = max(cntAB, wob(ab))
+            maxPw = max(maxPw, wob(p))
+            SC = max(SC, max(wob(p) + wob(cb), wob(ab)) + 2)
+            cb = ab if cb < 0 else max(ab, p + cb)
+    need_w = (SC + 63) // 64
+    wmax = 4 if need_w <= 4 else 8 if need_w <= 8 else 12 if need_w <= 12 else 16 if need_w <= 16 else 24
+    nc = 0
+    for k, rec in ((7, 64), (13, 64), (25, 128)):  # MfmaCfg<NC>: kChunks, kRecWords
+        if maxPw <= 2 * k - 1 and cntAB <= 64 and cntX <= 32 and cntX + maxPw + cntAB + 2 <= rec:
+            nc = k
+            break
+    return dict(cntX=cntX, maxPw=maxPw, SC=SC, need_w=need_w, wmax=wmax,
+                pad=need_w <= 24 and maxPw <= 25, nc=nc)
+
+
+# ------------------------------------------------------------------ traces (from the integers)
+def gate_trace(A, B):
+    """Per (value, bit): (na, nb) words of the operands the gate kernel multiplies; the product
+    spans nout = na + nb words, the uniform operand is a_i (nu = na)."""
+    return [[(words(a), words(b)) for a, b in zip(x, y)] for x, y in zip(A, B)]
+
+
+def borrow_trace(a, b, signed=False, eq=False):
+    """Per bit of one value, as borrow_kernel runs it: na, nb, np (words of p_i), nw (words of
+    the borrow or equality prefix going in) and nout = np + nw of the product p_i w_i."""
+    rows, w = [], 1 if eq else 0
+    n = len(a)
+    for i in range(n):
+        p = a[i] ^ b[i] ^ 1
+        rows.append(dict(i=i, na=words(a[i]), nb=words(b[i]), np=words(p), nw=words(w),
+                         nout=words(p) + words(w)))
+        if eq:
+            w = model.clmul_fast(p, w)
+        else:
+            gen = a[i] if signed and i == n - 1 else b[i]
+            w = model.clmul_fast(a[i], b[i]) ^ gen ^ model.clmul_fast(p, w)
+    return rows
+
+
+def add_trace(a, b):
+    """Per bit i < L - 1 of one value, as the carry chain runs it: words of x_i, P_i, a_i b_i, the
+    carry going in, and of the product P_i carry_i."""
+    rows, c = [], 0
+    for i in range(len(a)):
+        x = a[i] ^ b[i]
+        if i + 1 == len(a):
+            rows.append(dict(i=i, nx=words(x), np=0, nab=0, nc=words(c), nprod=0))
+            break
+        ab = model.clmul_fast(a[i], b[i])
+        p = model.clmul_fast(x, ab ^ 1)
+        rows.append(dict(i=i, nx=words(x), np=words(p), nab=words(ab), nc=words(c),
+                         nprod=words(p) + words(c) if p and c else 0))
+        c = ab ^ model.clmul_fast(p, c)
+    return rows
+
+
+# ------------------------------------------------------------------ reference circuits
+def gate_circuit(op, a, b):
+    if op == "and":
+        return [model.clmul_fast(x, y) for x, y in zip(a, b)]
+    if op == "or":
+        return [x ^ y ^ model.clmul_fast(x, y) for x, y in zip(a, b)]
+    if op == "xor":
+        return [x ^ y for x, y in zip(a, b)]
+    return [x ^ 1 for x in a]
+
+
+def mul_ref(a, b, signed=False):
+    return model.mul_circuit(a, b, signed=signed, mul=model.clmul_fast)
+
+
+# ------------------------------------------------------------------ the case table
+GATE_OPS = ("and", "or", "xor", "not")
+
+
+def _per_bit_gate():
+    i = np.arange(8)
+    return u32(64 * i + 63), u32(1000 - 97 * i)
+
+
+GATE_CASES = {
+    # name: (a bounds, b bounds)
+    "chunks": (uniform(8, 700), uniform(8, 700)),
+    "w1_edge": (uniform(8, 1023), uniform(8, 1023)),
+    "w2_edge": (uniform(8, 1023), uniform(8, 1055)),
+    "one_tile": (uniform(8, 8191), uniform(8, 8191)),
+    "multi_tile": (uniform(8, 8191), uniform(8, 8223)),
+    "lopsided": (uniform(8, 40), uniform(8, 9000)),
+    "lopsided_swapped": (uniform(8, 9000), uniform(8, 40)),
+    "per_bit": _per_bit_gate(),
+}
+
+
+def _u16_borrow_bounds():
+    """Per-bit bounds spread over 63..1100, different per operand: on every bit one operand is
+    near the top of the range and the other on a 64-step ladder from 63 up, alternating.  The
+    borrow's degree grows by max(ba_i, bb_i) per bit, so a spread whose per-bit maximum averages
+    below 16384 / 17 = 964 could not take the last borrow past 512 words; this one averages about
+    1080 (the last product p_15 w_15 has degree ba_0 + bb_0 + sum_{i>=1} max(ba_i, bb_i) = 17328,
+    542 words)."""
+    i = np.arange(16)
+    hi, lo = 1100 - 3 * i, 63 + 64 * i
+    ba = np.where(i % 2 == 0, hi, lo)
+    bb = np.where(i % 2 == 0, lo, hi)
+    return u32(ba), u32(bb)
+
+
+BORROW_CASES = {
+    # name: (a bounds, b bounds, scheduled + random values, FULL / bound - 1 pairs)
+    "u8_b700": (uniform(8, 700), uniform(8, 700), 9, 2),
+    "u16_per_bit": _u16_borrow_bounds() + (8, 2),
+    "u8_pair_b255": (uniform(8, 255), uniform(8, 255), 0, 8),
+}
+
+ADD_UNIFORM = (138, 139, 266, 267, 522, 523)
+ADD_MAXPW = {138: 13, 139: 14, 266: 25, 267: 26, 522: 49, 523: 50}
+
+
+def _last_wide(top):
+    ba = uniform(8, 128)
+    ba[7] = top
+    return ba, uniform(8, 128)
+
+
+def _add_per_bit():
+    rng = np.random.default_rng(SEED + 7)
+    return (u32(rng.integers(64, 267, size=8)), u32(rng.integers(64, 267, size=8)))
+
+
+ADD_CASES = {f"u8_b{B}": (uniform(8, B), uniform(8, B), 8, 4) for B in ADD_UNIFORM}
+ADD_CASES.update({
+    "u16_b266": (uniform(16, 266), uniform(16, 266), 8, 2),
+    "u32_b266": (uniform(32, 266), uniform(32, 266), 2, 2),
+    "last_1023": _last_wide(1023) + (8, 4),
+    "last_1024": _last_wide(1024) + (8, 4),
+    "per_bit": _add_per_bit() + (8, 4),
+})
+
+
+def _mul_per_bit(nbits, seed):
+    rng = np.random.default_rng(seed)
+    return (u32(rng.integers(64, 201, size=nbits)), u32(rng.integers(64, 201, size=nbits)))
+
+
+MUL_CASES = {
+    # name: (a bounds, b bounds, signed, k (mul_low) or None, scheduled + random, pairs)
+    "u8_b128": (uniform(8, 128), uniform(8, 128), False, None, 8, 2),
+    "i8_b128": (uniform(8, 128), uniform(8, 128), True, None, 8, 2),
+    "u8_per_bit": _mul_per_bit(8, SEED + 11) + (False, None, 8, 2),
+    "u16_low4_per_bit": _mul_per_bit(16, SEED + 12) + (False, 4, 8, 2),
+}
+
+DEC_CASES = {
+    # name: per-bit bounds (u8, n = 64)
+    "b511_ucap": uniform(8, 511),
+    "b512": uniform(8, 512),
+    "per_bit": u32([63, 482, 902, 1321, 1741, 2160, 2580, 3000]),
+    "per_bit_cap32": u32([63, 346, 629, 913, 1196, 1480, 1763, 2047]),
+}
+DEC_N = 64
+
+
+def _seed(family, name):
+    return SEED + sum(ord(c) * (k + 1) for k, c in enumerate(family + "/" + name)) % 100000
+
+
+@functools.lru_cache(maxsize=None)
+def inputs(family, name):
+    """dict(ba, bb, A, B, n, nbits) of a case (model form), made once."""
+    if family == "gate":
+        ba, bb = GATE_CASES[name]
+        ns, npair = 8, 2
+    elif family == "borrow":
+        ba, bb, ns, npair = BORROW_CASES[name]
+    elif family == "add":
+        ba, bb, ns, npair = ADD_CASES[name]
+    elif family == "mul":
+        ba, bb, _, _, ns, npair = MUL_CASES[name]
+    elif family == "dec":
+        ba = bb = DEC_CASES[name]
+        ns, npair = DEC_N, 0
+    else:
+        raise KeyError(family)
+    A, B = batch(ba, bb, ns, npair, _seed(family, name))
+    return dict(ba=u32(ba), bb=u32(bb), A=A, B=B, n=len(A), nbits=len(ba))
+
+
+def packed(family, name):
+    """The case's operands in the batch layout: (la, da, lb, db)."""
+    c = inputs(family, name)
+    return bm.pack(c["A"], c["ba"]) + bm.pack(c["B"], c["bb"])
+
+
+def _frozen(l, d):
+    l.setflags(write=False)
+    d.setflags(write=False)
+    return l, d
+
+
+@functools.lru_cache(maxsize=None)
+def gate_reference(name, op):
+    """(out bounds, limbs, degree words) of the model's gate on the case."""
+    c = inputs("gate", name)
+    ob = gate_bounds(op, c["ba"], c["bb"])
+    vals = [gate_circuit(op, a, b) for a, b in zip(c["A"], c["B"])]
+    return (ob, vals) + _frozen(*bm.pack(vals, ob))
+
+
+@functools.lru_cache(maxsize=None)
+def borrow_reference(name, op, signed=False):
+    """op: "sub" or a comparison.  (out bounds, values, limbs, degree words)."""
+    c = inputs("borrow", name)
+    if op == "sub":
+        ob = bm.sub_bounds(c["ba"], c["bb"])
+        vals = [bm.sub_circuit(a, b) for a, b in zip(c["A"], c["B"])]
+    else:
+        ob = bm.compare_bounds(op, c["ba"], c["bb"])
+        vals = [bm.bool_value(bm.compare_circuit(op, a, b, signed))
+                for a, b in zip(c["A"], c["B"])]
+    return (ob, vals) + _frozen(*bm.pack(vals, ob))
+
+
+@functools.lru_cache(maxsize=None)
+def add_reference(name):
+    c = inputs("add", name)
+    ob = add_bounds(c["ba"], c["bb"])
+    vals = [model.add_circuit(a, b) for a, b in zip(c["A"], c["B"])]
+    return (ob, vals) + _frozen(*bm.pack(vals, ob))
+
+
+@functools.lru_cache(maxsize=None)
+def mul_reference(name):
+    c = inputs("mul", name)
+    _, _, signed, k, _, _ = MUL_CASES[name]
+    k = k or c["nbits"]
+    ob = mul_bounds(c["ba"][:k], c["bb"][:k])
+    vals = [mul_ref(a[:k], b[:k], signed) for a, b in zip(c["A"], c["B"])]
+    return (ob, vals) + _frozen(*bm.pack(vals, ob))
+
+
+@functools.lru_cache(maxsize=None)
+def dec_reference(name):
+    """The plaintext bytes of the case's operand a under the DEC_PARAMS key (the model's
+    decipher_bit; test_synth_reference.py pins it to oracle.decrypt_batch)."""
+    c = inputs("dec", name)
+    s, _ = model.keygen(*DEC_PARAMS, SEED)
+    out = np.array([[bm.decrypt_value(bits, s)] for bits in c["A"]], dtype=np.uint8)
+    out.setflags(write=False)
+    return out
+
+
+# ------------------------------------------------------------------ path assertions
+def check_gate_path(name):
+    """The path each gate case is named for (gate_kernel: wave_mul<kQSmall = 10, 8>(a_i, na, b_i,
+    nb, ...), nout = na + nb, W = ceil(nout / 64) capped at 8, further tiles MULTI)."""
+    c = inputs("gate", name)
+    t = [r for v in gate_trace(c["A"], c["B"]) for r in v]
+    nu, nout = max(r[0] for r in t), max(r[0] + r[1] for r in t)
+    tile_w = min(8, (nout + 63) // 64)
+    if name == "chunks":
+        assert nu == 22 and (nu + 9) // 10 == 3
+    elif name == "w1_edge":
+        assert nout == 64 and tile_w == 1
+    elif name == "w2_edge":
+        assert nout == 65 and tile_w == 2
+    elif name == "one_tile":
+        assert nout == 512 and tile_w == 8 and nout <= 64 * 8
+    elif name == "multi_tile":
+        assert nout == 513 and nout > 64 * 8
+    elif name == "lopsided":
+        assert nu == 2 and max(r[1] for r in t) == 282
+    elif name == "lopsided_swapped":
+        assert nu == 282 and max(r[1] for r in t) == 2
+    elif name == "per_bit":
+        ca, cb = c["ba"] // 64 + 1, c["bb"] // 64 + 1
+        # within an operand every capacity is distinct, and past bit 0 the two operands never
+        # share an offset
+        assert len(set(ca.tolist())) == 8 and len(set(cb.tolist())) == 8
+        assert not (np.cumsum(ca)[:-1] == np.cumsum(cb)[:-1]).any()
+        for i in range(8):  # and every bit's slot is filled by some value
+            assert max(r[i][0] for r in gate_trace(c["A"], c["B"])) == int(c["ba"][i]) // 32 + 1
+            assert max(r[i][1] for r in gate_trace(c["A"], c["B"])) == int(c["bb"][i]) // 32 + 1
+    # the OR scratch Xs = T + na + nb + 2 starts as far in as the case's widest product
+    return dict(nu=nu, nout=nout)
+
+
+def check_borrow_path(name):
+    """borrow_kernel: the generate product wave_mul<kQSmall, 8>(a_i, na, b_i, nb, ...) and the
+    propagate product wave_mul<kQSmall, 8>(p_i, np, w_i, nw, ...); borrow_run's slots SA = SB = SX
+    = 2 cap and cw = SX + chain / 32 + 3."""
+    c = inputs("borrow", name)
+    lt = [borrow_trace(a, b) for a, b in zip(c["A"], c["B"])]
+    rows = [r for t in lt for r in t]
+    na, np_, nout = (max(r[k] for r in rows) for k in ("na", "np", "nout"))
+    slot = 2 * int(max(c["ba"].max(), c["bb"].max()) // 64 + 1)
+    chain = bm.borrow_bounds(c["ba"], c["bb"], c["nbits"])[-1]
+    if name == "u8_b700":
+        assert na == 22 and (na + 9) // 10 == 3 and np_ == 22 and slot == 22
+        # the last product p_7 w_7 is as long as the bounds allow: the borrow buffers are filled
+        assert nout == 22 + bm.borrow_bounds(c["ba"], c["bb"], 7)[-1] // 32 + 1 == 198
+    elif name == "u16_per_bit":
+        assert lt[-1][-1]["nout"] > 512, lt[-1][-1]  # p_15 w_15: a MULTI tile
+        assert nout == max(t[-1]["nout"] for t in lt)
+        for k, bnd in (("na", c["ba"]), ("nb", c["bb"])):  # every bit's slot is filled
+            for i in range(16):
+                assert max(t[i][k] for t in lt) == int(bnd[i]) // 32 + 1
+    elif name == "u8_pair_b255":
+        assert all(r["na"] == 8 and r["np"] == 8 for r in rows) and slot == 8
+        assert all(a[i].bit_length() - 1 == 255 for a in c["A"] for i in range(8))
+    return dict(na=na, np=np_, nout=nout, chain=chain)
+
+
+def check_add_path(name):
+    """hm_add_batch's plan limits (capi.cpp: maxPw <= 2 NC - 1, cntX <= 32, PAD: maxPw <= 25,
+    wmax from need_w = ceil(SC / 64)) and data that reaches them."""
+    c = inputs("add", name)
+    plan = add_plan(c["ba"], c["bb"])
+    tr = [add_trace(a, b) for a, b in zip(c["A"], c["B"])]
+    rows = [r for t in tr for r in t]
+    npw, nx, nprod = (max(r[k] for r in rows) for k in ("np", "nx", "nprod"))
+    # the data fills the plan's slots (where ba_i = bb_i the tops cancel in x_i, so P_i stops one
+    # short of its bound: that costs a word only where the bound is a multiple of 32)
+    reach = max((max(a, b) + a + b - (a == b)) // 32 + 1
+                for a, b in zip(map(int, c["ba"][:-1]), map(int, c["bb"][:-1])))
+    assert npw == reach >= plan["maxPw"] - 1 and nx == plan["cntX"]
+    if name.startswith("u8_b"):
+        B = int(name[4:])
+        assert npw == ADD_MAXPW[B]
+        assert plan["nc"] == {138: 7, 139: 13, 266: 13, 267: 25, 522: 25, 523: 0}[B]
+        assert plan["pad"] == (B <= 266)
+    elif name in ("u16_b266", "u32_b266"):
+        assert npw == 25 and plan["nc"] == 13 and plan["pad"]
+        assert (plan["SC"], plan["need_w"], plan["wmax"]) == ((368, 6, 8) if name == "u16_b266"
+                                                              else (767, 12, 12))
+        assert plan["SC"] - 2 - nprod <= 1  # the widest product fills the carry buffer
+    elif name == "last_1023":
+        assert plan["cntX"] == 32 and plan["nc"] == 7
+        assert max(t[7]["nx"] for t in tr) == 32  # x_7's 32nd word is live
+    elif name == "last_1024":
+        assert plan["cntX"] == 33 and plan["nc"] == 0
+        assert max(t[7]["nx"] for t in tr) == 33
+    elif name == "per_bit":
+        assert plan["nc"] in (7, 13) and plan["pad"]
+        assert len(set((c["ba"] // 64).tolist() + (c["bb"] // 64).tolist())) >= 3
+        for i in range(8):  # every bit's slot is filled
+            assert max(t[i]["nx"] for t in tr) == int(max(c["ba"][i], c["bb"][i])) // 32 + 1
+    return dict(plan, np=npw, nx=nx, nprod=nprod)
+
+
+def check_mul_path(name):
+    """Every kind reaches every column: a NULL and a UNIT partial product and an ONES operand in
+    each bit position of each operand (the schedule), and operands that fill their bounds."""
+    c = inputs("mul", name)
+    nb = c["nbits"]
+    for X, bnd, shift in ((c["A"], c["ba"], 0), (c["B"], c["bb"], 3)):
+        for i in range(nb):
+            col = [X[e][i] for e in range(8)]
+            assert 0 in col and 1 in col and (1 << (int(bnd[i]) + 1)) - 1 in col
+            assert max(p.bit_length() - 1 for p in col) == int(bnd[i])
+    caps = np.concatenate([c["ba"] // 64 + 1, c["bb"] // 64 + 1])
+    if "per_bit" in name:
+        assert len(set(caps.tolist())) >= 2 and (c["ba"] // 64 != c["bb"] // 64).any()
+    return dict(caps=caps)
+
+
+def check_dec_path(name):
+    """hm_decrypt_batch: D.ucap = the common capacity when all are equal and <= 8 limbs."""
+    c = inputs("dec", name)
+    caps = (c["ba"] // 64 + 1).tolist()
+    ucap = caps[0] if len(set(caps)) == 1 and caps[0] <= 8 else 0
+    assert ucap == {"b511_ucap": 8, "b512": 0, "per_bit": 0, "per_bit_cap32": 0}[name]
+    if name == "b512":
+        assert caps == [9] * 8
+    if name == "per_bit":  # launch_decrypt: maxcap > 32, one wave per value (decrypt_kernel)
+        assert len(set(caps)) == 8 and caps[0] == 1 and caps[-1] == 47
+    if name == "per_bit_cap32":  # maxcap = 32, the last on decrypt_bits_kernel
+        assert len(set(caps)) == 8 and caps[0] == 1 and caps[-1] == 32
+    for i in range(8):  # some polynomial reaches the last bit of every bit's capacity-defining bound
+        assert max(v[i].bit_length() - 1 for v in c["A"]) == int(c["ba"][i])
+    return dict(ucap=ucap)

@@ -50,10 +50,13 @@ def _rand_polys(rng, n, cap, maxdeg=None):
 
 @pytest.mark.parametrize("ca,cb", [(1, 1), (5, 5), (3, 17), (40, 2), (200, 9), (400, 400)])
 def test_poly_mul_add(H, oracle, ca, cb):
-    import torch
     rng = np.random.default_rng(ca * 1000 + cb)
     n = 64
-    A, B = _rand_polys(rng, n, ca), _rand_polys(rng, n, cb)
+    _check_poly_mul_add(H, oracle, _rand_polys(rng, n, ca), _rand_polys(rng, n, cb))
+
+
+def _check_poly_mul_add(H, oracle, A, B):
+    n = len(A)
     ctx = make_ctx(H, (64, 64, 1, 64), 1)
     dev = ctx.device
     pa, pb = H.Polys.from_host(A, dev), H.Polys.from_host(B, dev)
@@ -71,6 +74,25 @@ def test_poly_mul_add(H, oracle, ca, cb):
         assert sd[i] == rdeg
         w = min(len(ref), sl.shape[1])
         assert np.array_equal(sl[i, :w], ref[:w]) and not sl[i, w:].any()
+
+
+@pytest.mark.parametrize("ca,cb", [(16, 16), (16, 17), (128, 128), (128, 129)])
+def test_poly_mul_add_edges(H, oracle, ca, cb):
+    """Operands that fill their capacity, at the tile edges of poly_mul_kernel's wave_mul<kQBig, 8>:
+    64 / 66 output words (the last W = 1 product and a W = 2 one) and 512 / 514 (exactly one W = 8
+    tile, and a second, MULTI tile).  Every pairing of a random polynomial of degree 64 cap - 1,
+    the monomial X^(64 cap - 1) and the all-ones polynomial (the densest decision bits)."""
+    import synth
+    rng = np.random.default_rng(ca * 1000 + cb)
+
+    def rows(cap):
+        b = 64 * cap - 1
+        return [synth.model.int_to_limbs(synth.poly(k, b, rng), cap) for k in ("FULL", "MONO", "ONES")]
+    A = np.array([r for r in rows(ca) for _ in range(3)], dtype=np.uint64)
+    B = np.array(rows(cb) * 3, dtype=np.uint64)
+    assert 2 * (ca + cb) == {(16, 16): 64, (16, 17): 66, (128, 128): 512, (128, 129): 514}[ca, cb]
+    assert all(int(r[-1]) >> 63 for r in A) and all(int(r[-1]) >> 63 for r in B)
+    _check_poly_mul_add(H, oracle, A, B)
 
 
 @pytest.mark.parametrize("cap,sdeg", [(1, 1), (3, 128), (20, 128), (9, 63), (9, 64), (50, 700),

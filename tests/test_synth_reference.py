@@ -1,0 +1,179 @@
+"""CPU: the references of the full-bounds tier (tests/synth.py), pinned before the GPU meets them.
+
+For every case of test_gpu_full_bounds.py: the model's result equals the C oracle's on the same
+synthetic operands (borrow_model has no second implementation: its ring identities and residues
+are checked instead), every output degree is within the engine's static output bounds
+(H.*_out_bounds, which the Python restatements of synth.py must equal), and the case's path
+assertion holds on the model's integers, so a case that stops reaching its path fails here.
+"""
+import numpy as np
+import pytest
+
+import borrow_model as bm
+import synth
+from helpers import assert_batches_equal, residue_modulus
+
+
+@pytest.fixture(scope="module")
+def H():
+    import homomorph
+    homomorph.lib()  # host-only entry points: no GPU needed
+    return homomorph
+
+
+def within(vals, ob):
+    for v in vals:
+        for p, b in zip(v, ob):
+            assert p.bit_length() - 1 <= int(b)
+
+
+# ------------------------------------------------------------------ the generator itself
+def test_schedule_and_kinds():
+    """Every kind at every bit position, exact degrees, nothing above the bound."""
+    for bound in (0, 1, 31, 40, 63, 64, 255, 700, 1023, 8223):
+        b8 = synth.uniform(8, bound)
+        vals = synth.operands(b8, 12, 5)
+        within(vals, b8)
+        for e in range(8):
+            for i in range(8):
+                k, p = synth.kind_of(e, i), vals[e][i]
+                assert k == synth.KINDS[(e + i) % 8]
+                if k in ("FULL", "MONO", "ONES", "SPARSE"):
+                    assert p.bit_length() - 1 == bound
+                if k == "MONO":
+                    assert p == 1 << bound
+                if k == "ONES":
+                    assert p == (1 << (bound + 1)) - 1
+                if k == "NULL":
+                    assert p == 0
+                if k == "UNIT":
+                    assert p == 1
+                if k == "EDGE":
+                    assert p.bit_length() - 1 in synth.edge_degrees(bound)
+                if k == "SPARSE" and bound >= 2:
+                    assert 1 <= p.bit_count() <= 3
+                if k == "LOW" and bound >= 2:
+                    assert p.bit_length() - 1 < bound // 2
+        for i in range(8):
+            assert {synth.kind_of(e, i) for e in range(8)} == set(synth.KINDS)
+            assert {synth.kind_of(e, i, 3) for e in range(8)} == set(synth.KINDS)
+    assert synth.edge_degrees(700) == [31, 32, 33, 63, 64, 65, 639, 640, 699]
+    assert synth.operands(synth.uniform(8, 300), 10, 7) == synth.operands(synth.uniform(8, 300), 10, 7)
+    A, B = synth.full_pair(synth.uniform(8, 266), synth.uniform(8, 266), 4, 1)
+    assert all(a.bit_length() - 1 == 266 for v in A for a in v)
+    assert all(b.bit_length() - 1 == 265 for v in B for b in v[1:])
+    assert [v[0].bit_length() - 1 for v in B] == [265, 266, 265, 266]
+
+
+# ------------------------------------------------------------------ gates
+@pytest.mark.parametrize("name", list(synth.GATE_CASES))
+def test_gate_reference(H, oracle, name):
+    c = synth.inputs("gate", name)
+    la, da, lb, db = synth.packed("gate", name)
+    assert 8 <= c["n"] <= 16
+    for op in synth.GATE_OPS:
+        ob, vals, rl, rd = synth.gate_reference(name, op)
+        opcls = {"and": H.HomomorphicAndGate, "or": H.HomomorphicOrGate,
+                 "xor": H.HomomorphicXorGate, "not": H.HomomorphicNotGate}[op]
+        assert np.array_equal(ob, H.gate_out_bounds(opcls, c["ba"], None if op == "not" else c["bb"]))
+        within(vals, ob)
+        ol, od = oracle.gate_batch(op, la, da, c["ba"], lb, db, c["bb"], 8, c["n"], ob)
+        assert_batches_equal(rl, rd, ol, od, ob, c["n"], f"{name} {op}")
+    synth.check_gate_path(name)
+
+
+# ------------------------------------------------------------------ subtraction, comparisons
+@pytest.mark.parametrize("name", list(synth.BORROW_CASES))
+def test_borrow_reference(H, name):
+    c = synth.inputs("borrow", name)
+    assert 8 <= c["n"] <= 16
+    g = residue_modulus(17)
+    mul = synth.model.residue_mul(g)
+    RA = [[synth.model.residue_int(p, g) for p in v] for v in c["A"]]  # once: the slow part
+    RB = [[synth.model.residue_int(p, g) for p in v] for v in c["B"]]
+    ob, vals, _, _ = synth.borrow_reference(name, "sub")
+    assert np.array_equal(ob, H.sub_out_bounds(c["ba"], c["bb"]))
+    within(vals, ob)
+    for a, b, ra, rb, out in zip(c["A"], c["B"], RA, RB, vals):
+        w = bm.borrows(a, b, last=False)
+        assert [o ^ x ^ y for o, x, y in zip(out, a, b)] == w  # sub_i + a_i + b_i = w_i
+        # the borrow recurrence in the residue ring (a ring homomorphism)
+        rw = 0
+        for i in range(len(a)):
+            assert synth.model.residue_int(w[i], g) == rw
+            rw = mul(ra[i], rb[i]) ^ rb[i] ^ mul(ra[i] ^ rb[i] ^ 1, rw)
+    for signed in (False, True):
+        for op in bm.COMPARISONS:
+            ob, vals, _, _ = synth.borrow_reference(name, op, signed)
+            assert np.array_equal(ob, H.compare_out_bounds(_cmp(H, op), c["ba"], c["bb"]))
+            within(vals, ob)
+            for ra, rb, out in zip(RA, RB, vals):
+                if op in ("eq", "ne"):
+                    want = 1
+                    for x, y in zip(ra, rb):
+                        want = mul(x ^ y ^ 1, want)
+                    want ^= op == "ne"
+                else:
+                    if op in ("gt", "le"):
+                        ra, rb = rb, ra
+                    want, n = 0, len(ra)
+                    for i in range(n):
+                        gen = ra[i] if signed and i == n - 1 else rb[i]
+                        want = mul(ra[i], rb[i]) ^ gen ^ mul(ra[i] ^ rb[i] ^ 1, want)
+                    want ^= op in ("ge", "le")
+                assert synth.model.residue_int(out[0], g) == want, (op, signed)
+                assert out[1:] == [0] * 7
+    synth.check_borrow_path(name)
+
+
+def _cmp(H, op):
+    return {"eq": H.HomomorphicEqual, "ne": H.HomomorphicNotEqual, "lt": H.HomomorphicLessThan,
+            "le": H.HomomorphicLessEqual, "gt": H.HomomorphicGreaterThan,
+            "ge": H.HomomorphicGreaterEqual}[op]
+
+
+# ------------------------------------------------------------------ addition
+@pytest.mark.parametrize("name", list(synth.ADD_CASES))
+def test_add_reference(H, oracle, name):
+    c = synth.inputs("add", name)
+    la, da, lb, db = synth.packed("add", name)
+    ob, vals, rl, rd = synth.add_reference(name)
+    assert np.array_equal(ob, H.add_out_bounds(c["ba"], c["bb"]))
+    within(vals, ob)
+    ol, od = oracle.add_batch(la, da, c["ba"], lb, db, c["bb"], c["nbits"], c["n"], ob)
+    assert_batches_equal(rl, rd, ol, od, ob, c["n"], name)
+    synth.check_add_path(name)
+
+
+# ------------------------------------------------------------------ multiplication
+@pytest.mark.parametrize("name", list(synth.MUL_CASES))
+def test_mul_reference(H, oracle, name):
+    from helpers import low_bits
+    c = synth.inputs("mul", name)
+    _, _, signed, k, _, _ = synth.MUL_CASES[name]
+    la, da, lb, db = synth.packed("mul", name)
+    ba, bb, nbits = c["ba"], c["bb"], c["nbits"]
+    if k:
+        la, da, ba = low_bits(la, da, ba, c["n"], k)
+        lb, db, bb = low_bits(lb, db, bb, c["n"], k)
+        nbits = k
+    ob, vals, rl, rd = synth.mul_reference(name)
+    assert np.array_equal(ob, H.mul_out_bounds(ba, bb, signed))
+    within(vals, ob)
+    ol, od = oracle.mul_batch(la, da, ba, lb, db, bb, nbits, c["n"], ob, signed=signed)
+    assert_batches_equal(rl, rd, ol, od, ob, c["n"], name)
+    synth.check_mul_path(name)
+
+
+# ------------------------------------------------------------------ decryption
+@pytest.mark.parametrize("name", list(synth.DEC_CASES))
+def test_dec_reference(oracle, name):
+    c = synth.inputs("dec", name)
+    la, da, _, _ = synth.packed("dec", name)
+    sk, _, _ = oracle.keygen(*synth.DEC_PARAMS, synth.SEED)
+    s, _ = synth.model.keygen(*synth.DEC_PARAMS, synth.SEED)
+    assert synth.model.limbs_to_int(sk) == s
+    want = oracle.decrypt_batch(sk, la, da, c["ba"], 8, c["n"])
+    assert np.array_equal(synth.dec_reference(name), want)
+    assert 0 < int(np.unpackbits(want).sum()) < want.size * 8  # neither all zeros nor all ones
+    synth.check_dec_path(name)
