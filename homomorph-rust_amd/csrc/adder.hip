@@ -1,6 +1,8 @@
 // adder.hip — gfx950 kernels of the ripple-carry adder (src/impls/numbers/common.rs:37-56):
 //   add_prep_kernel          carry-independent part: ab_i, P_i, x_i for every bit, lanes over
 //                            (bit, word), several waves per value
+//   add_prep_uniform_kernel  the same for operands of one uniform bound (fresh ciphertexts):
+//                            compile-time slots, degrees by arithmetic
 //   add_chain_staged_kernel / add_chain_kernel
 //                            the carry chain carry' = ab_i ^ P_i * carry, one wavefront per
 //                            value, carry kept in LDS, products by scalar-decided VALU XORs
@@ -266,6 +268,143 @@ __global__ void __launch_bounds__(256) add_prep_kernel(AddArgs A) {
     }
 }
 
+// The prep for operands of ONE uniform bound (AddArgs.ucap = CAP limbs per bit of both operands,
+// with the top-word copies: the bound is 64 (CAP - 1), fresh ciphertexts of d + d' = 64 (CAP - 1)).
+// Same launch geometry, LDS slots, workspace and product rows as add_prep_kernel<0, 0, true>, but
+// every slot size and offset is arithmetic in compile-time constants -- no Bounds reads, no bit
+// cursors, no runtime divisors -- and the products' degrees come from the inputs' (GF(2)[X] has
+// no zero divisors), not from scans of the product words:
+//   ab_i null iff a_i or b_i is; else deg ab_i = deg a_i + deg b_i
+//   deg x_i   from x's own words, one clz per staging lane (the inputs' tops may cancel)
+//   P_i = x_i ^ x_i ab_i: null if x_i is, x_i if ab_i is null, else deg x_i + deg ab_i
+//   (ab_i = 1 forces a_i = b_i = 1, so x_i = 0)
+// The P slots start as x_i (written by the staging lanes) and the rows add x_i ab_i, so the ab and
+// P slots leave as straight copies.
+template <int CAP>
+__global__ void __launch_bounds__(256) add_prep_uniform_kernel(AddArgs A) {
+    constexpr uint32_t kBound = 64u * (CAP - 1);
+    constexpr uint32_t cA = 2 * CAP, cX = 2 * CAP - 1, cAB = 4 * CAP - 3, cP = 6 * CAP - 5;
+    constexpr uint32_t cq = cX - 1, qt = cX - 1; // product rows per bit; the top word's index
+    extern __shared__ uint32_t lds[];
+    const uint32_t wave = rfl(threadIdx.x >> 6);
+    const uint64_t gw = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint32_t L = A.nbits;
+    uint64_t e;
+    uint32_t part;
+    if ((gw >> 32) == 0) // (the 64-bit division is a long routine)
+        e = (uint32_t)gw / A.wpv, part = (uint32_t)gw % A.wpv;
+    else
+        e = gw / A.wpv, part = (uint32_t)(gw % A.wpv);
+    if (e >= A.n) return;
+    // this wave's slots [0, nmine) = bits [i0, i0 + nmine); products for bits < L - 1
+    const uint32_t bpw = (L + A.wpv - 1) / A.wpv;
+    const uint32_t i0 = rfl(min(L, part * bpw)), nmine = rfl(min(L, i0 + bpw) - i0);
+    const uint32_t nprod = rfl(min(nmine, (L - 1) - min(i0, L - 1)));
+    // lanes over f in [0, n), n wave-uniform: a scalar loop, one EXEC test per pass
+    auto lanes = [&](uint32_t n, auto &&body) {
+        for (uint32_t f0 = 0; f0 < n; f0 += kWave)
+            if (f0 + lane < n) body(f0 + lane);
+    };
+    // LDS: [a: bpw cA][b: bpw cA][x: bpw cX][ab: bpw cAB][P: bpw cP][words of a, b, x, ab; deg x + 1]
+    uint32_t *Ls = lds + (size_t)wave * A.prep_lds;
+    uint32_t *Al = Ls, *Bl = Al + bpw * cA, *Xl = Bl + bpw * cA;
+    uint32_t *ABl = Xl + bpw * cX, *Pl = ABl + bpw * cAB;
+    uint32_t *nAl = Pl + bpw * cP, *nBl = nAl + bpw, *nXl = nBl + bpw, *nABl = nXl + bpw;
+    uint32_t *dXl = nABl + bpw;
+    // a value's workspace: [ab: L cAB][P: L cP][deg ab: L][deg P: L][x: L cX]
+    const size_t oP = (size_t)L * cAB, oDA = oP + (size_t)L * cP, oDP = oDA + L, oX = oDP + L;
+    uint32_t *ws = A.ws + e * A.ws_stride;
+    const uint64_t *pa = A.a.limbs + e * A.a.stride + (size_t)i0 * CAP;
+    const uint64_t *pb = A.b.limbs + e * A.b.stride + (size_t)i0 * CAP;
+    const uint32_t *da = A.a.degree + e * L + i0, *db = A.b.degree + e * L + i0;
+
+    // one global round trip: the degrees, then the first two limbs per lane of both operands
+    uint32_t dga = 0, dgb = 0;
+    if (lane < nmine) dga = da[lane], dgb = db[lane];
+    const uint32_t tot = nmine * CAP; // the wave's bits are contiguous limbs of each operand
+    uint64_t fa[2], fb[2];
+#pragma unroll
+    for (uint32_t j = 0; j < 2; ++j) {
+        const uint32_t g = lane + j * kWave;
+        fa[j] = g < tot ? pa[g] : 0ull, fb[j] = g < tot ? pb[g] : 0ull;
+    }
+    // the rows' accumulators: ab slots, and the P slots' words above x
+    lanes(nprod * cAB, [&](uint32_t f) { ABl[f] = 0u; });
+    constexpr uint32_t cPz = cP - cX;
+    lanes(nprod * cPz, [&](uint32_t f) { Pl[f / cPz * cP + cX + f % cPz] = 0u; });
+    if (lane < nmine) nAl[lane] = dga, nBl[lane] = dgb, dXl[lane] = 0u;
+    wsync();
+    // stage + validate (every bit, the last one too); x_i to LDS, to the P slot and to the workspace
+    bool bad = false;
+    auto stage = [&](uint32_t g, uint64_t va, uint64_t vb) {
+        const uint32_t t = g / CAP, k = g % CAP;
+        va = checked_limb(va, nAl[t], kBound, k, bad);
+        vb = checked_limb(vb, nBl[t], kBound, k, bad);
+        *(uint2 *)(Al + t * cA + 2 * k) = make_uint2((uint32_t)va, (uint32_t)(va >> 32));
+        *(uint2 *)(Bl + t * cA + 2 * k) = make_uint2((uint32_t)vb, (uint32_t)(vb >> 32));
+        const uint64_t x = va ^ vb;
+        const uint32_t xl = (uint32_t)x, xh = (uint32_t)(x >> 32);
+        uint32_t *xs = Xl + t * cX + 2 * k, *xg = ws + oX + (size_t)(i0 + t) * cX + 2 * k;
+        uint32_t *xp = Pl + t * cP + 2 * k;
+        const bool prod = t < nprod;
+        xs[0] = xl, xg[0] = xl;
+        if (prod) xp[0] = xl;
+        if (k + 1 < CAP) { // (limb CAP - 1 holds bit 0 only: x has cX = 2 CAP - 1 words)
+            xs[1] = xh, xg[1] = xh;
+            if (prod) xp[1] = xh;
+        }
+        if (x) atomicMax(&dXl[t], 64 * k + 64 - (uint32_t)__builtin_clzll(x));
+    };
+#pragma unroll
+    for (uint32_t j = 0; j < 2; ++j)
+        if (lane + j * kWave < tot) stage(lane + j * kWave, fa[j], fb[j]);
+    for (uint32_t g0 = 2 * kWave; g0 < tot; g0 += kWave)
+        if (g0 + lane < tot) stage(g0 + lane, pa[g0 + lane], pb[g0 + lane]);
+    if (__any(bad) && lane == 0) flag(A.status, HM_ERR_BAD_INPUT);
+    wsync();
+    // degrees (+ 1, 0 = null) by arithmetic, word counts for the rows
+    if (lane < nmine) {
+        uint32_t a1 = dga + 1, b1 = dgb + 1;
+        if (dga > kBound || (dga == 0 && !(Al[lane * cA] & 1u))) a1 = 0;
+        if (dgb > kBound || (dgb == 0 && !(Bl[lane * cA] & 1u))) b1 = 0;
+        const uint32_t x1 = dXl[lane];
+        const uint32_t ab1 = a1 && b1 ? a1 + b1 - 1 : 0u;
+        const uint32_t p1 = !x1 ? 0u : !ab1 ? x1 : x1 + ab1 - 1;
+        nAl[lane] = (uint32_t)bitwords((int)a1), nBl[lane] = (uint32_t)bitwords((int)b1);
+        nXl[lane] = (uint32_t)bitwords((int)x1), nABl[lane] = (uint32_t)bitwords((int)ab1);
+        if (lane < nprod) ws[oDA + i0 + lane] = ab1, ws[oDP + i0 + lane] = p1;
+    }
+    wsync();
+    // phase 1: ab_i = a_i * b_i -- rows for a_i's words below the top one (lanes over (slot,
+    // word)), the top word (0 or 1, set exactly when a_i has cX words) as a copy of b_i
+    lanes(nprod * cq, [&](uint32_t f) {
+        const uint32_t t = f / cq, q = f % cq;
+        if (q < nAl[t]) clmul_row_xor(Al[t * cA + q], Bl + t * cA, (int)nBl[t], ABl + t * cAB + q);
+    });
+    lanes(nprod * cA, [&](uint32_t f) {
+        const uint32_t t = f / cA, k = f % cA;
+        if (k < nBl[t] && nAl[t] == cX) atomicXor(&ABl[t * cAB + qt + k], Bl[f]);
+    });
+    wsync();
+    // ab_i out (the wave's slots are one run in LDS and in the workspace), and phase 2's top word:
+    // P_i += ab_i shifted where x_i's bit 32 (cX - 1) is set
+    uint32_t *wsab = ws + (size_t)i0 * cAB, *wsp = ws + oP + (size_t)i0 * cP;
+    lanes(nprod * cAB, [&](uint32_t f) {
+        const uint32_t t = f / cAB, k = f % cAB;
+        const uint32_t w = ABl[f];
+        wsab[f] = w;
+        if (k < nABl[t] && (Xl[t * cX + qt] & 1u)) atomicXor(&Pl[t * cP + qt + k], w);
+    });
+    // phase 2: P_i = x_i ^ x_i * ab_i
+    lanes(nprod * cq, [&](uint32_t f) {
+        const uint32_t t = f / cq, q = f % cq;
+        if (q < nXl[t]) clmul_row_xor(Xl[t * cX + q], ABl + t * cAB, (int)nABl[t], Pl + t * cP + q);
+    });
+    wsync();
+    lanes(nprod * cP, [&](uint32_t f) { wsp[f] = Pl[f]; });
+}
+
 // s_i = a_i ^ b_i ^ carry, read straight from the input limbs (masked at the degrees, which the
 // prep kernel validated) and the LDS carry words; writes the output bit and its exact degree.
 __device__ __forceinline__ int store_sum_bit(const uint64_t *pa, uint32_t dga, const uint64_t *pb, uint32_t dgb,
@@ -405,7 +544,11 @@ int launch_add_prep(const AddArgs &a, void *stream) {
 #ifndef HM_PREP_FIXED
 #define HM_PREP_FIXED 0 // (A/B knob) 1: product rows at the slots' fixed lengths (measured neutral, r06)
 #endif
-    if (a.vpw > 1 && a.top1)
+    if (a.ucap == 5 && a.vpw <= 1)
+        hipLaunchKernelGGL((add_prep_uniform_kernel<5>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, a);
+    else if (a.ucap)
+        return -1; // (the plan chose an instance that does not exist)
+    else if (a.vpw > 1 && a.top1)
         hipLaunchKernelGGL((add_prep_kernel<0, 0, true, true>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, a);
     else if (a.vpw > 1)
         hipLaunchKernelGGL((add_prep_kernel<0, 0, false, true>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, a);

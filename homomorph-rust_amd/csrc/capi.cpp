@@ -869,8 +869,10 @@ hm_status hm_add_batch(hm_ctx *c, const hm_batch *a, const hm_batch *b, hm_batch
         auto waves = [&](uint32_t rows) { // rows: product rows per bit
             const uint64_t rows_fit = (L + std::max<uint32_t>(1, 64 / rows) - 1) /
                                       std::max<uint32_t>(1, 64 / rows);
+            // (never fewer than ceil(L / 64): a wave's range is at most 64 bits -- a u128 add with
+            // one row per bit at a big batch asked for 1)
             return (uint32_t)std::max<uint64_t>(
-                1, std::min<uint64_t>({std::max(want, (rows_fit + 1) / 2), 8, (uint64_t)L}));
+                (L + 63) / 64, std::min<uint64_t>({std::max(want, (rows_fit + 1) / 2), 8, (uint64_t)L}));
         };
         // the top word of every a_i, b_i, x_i holds at most bit 32 (cntX - 1) = maxb: the prep can
         // add its multiples as shifted copies instead of product rows -- worth it when the shorter
@@ -894,6 +896,19 @@ hm_status hm_add_batch(hm_ctx *c, const hm_batch *a, const hm_batch *b, hm_batch
                 A.vpw = v, A.top1 = t1ok;
                 while ((1u << A.lgL) < L) ++A.lgL;
             }
+        }
+        // both operands of one bound 64 (CAP - 1), as fresh ciphertexts of d + d' = 64 (CAP - 1)
+        // are: the uniform prep (adder.hip add_prep_uniform_kernel), whose slot sizes are
+        // compile-time and which always takes the top-word copies, whatever A.top1 says; CAP = 5
+        // is the instance built (the headline)
+        A.ucap = 0;
+        if (A.vpw == 1 && t1ok) {
+            const uint32_t ub = a->bound[0], cap = cap_of(ub);
+            bool uni = cap == 5 && ub == 64 * (cap - 1);
+            for (uint32_t i = 0; i < L && uni; ++i) uni = a->bound[i] == ub && b->bound[i] == ub;
+            if (uni && cntA == 2 * cap && cntB == 2 * cap && cntX == 2 * cap - 1 &&
+                cntAB == 4 * cap - 3 && cntP == 6 * cap - 5)
+                A.ucap = cap;
         }
         const uint32_t bpw = A.vpw > 1 ? A.vpw * L : (L + A.wpv - 1) / A.wpv;
         // (+ 2 bpw: with dAB / dP, stage_ab's bound / offset tables; a wave's range is at most 64 bits)

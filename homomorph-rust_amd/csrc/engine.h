@@ -48,6 +48,10 @@ struct AddArgs {
     uint32_t wpv;                     // prep: waves per value (bits are dealt round-robin)
     uint32_t vpw;                     // prep: > 1: values per wave instead (whole values, L = 2^lgL)
     uint32_t lgL;                     // prep: log2 nbits when vpw > 1
+    uint32_t ucap;                    // prep: > 0: every bit of a and of b has the one bound
+                                      // 64 (ucap - 1), ucap limbs (add_prep_uniform_kernel<ucap>:
+                                      // cntA = cntB = 2 ucap, cntX = 2 ucap - 1, cntAB = 4 ucap - 3,
+                                      // cntP = 6 ucap - 5, one value per wave or less)
     uint32_t prep_lds;                // prep: LDS words per wave
     uint32_t chain_lds;               // chain: LDS words per wave
     uint32_t staged;                  // chain: x, ab, P and degrees staged in LDS, carry in place
