@@ -295,8 +295,10 @@ struct MulMfmaArgs {
 };
 // Partial products grouped by their shared factor a_j (mul_mfma.hip mul_ppg_kernel): every
 // a_j * b_k of the plan in one launch before the columns, one wave per (value, a_j), a_j's A
-// fragments built once for all of its products (a_j within kMfPPGWords words: one chunk group).
-constexpr uint32_t kMfPPGWords = 34;
+// fragments built once for all of its products (a_j within kMfPPGWords words: one chunk group of
+// at most kMfPPGWords / 2 + 1 = 17 chunks, as many as the kernel holds A fragments for; 34 words
+// would be 18).  Wider operands take the per-column launches (mul_host.cpp ppm).
+constexpr uint32_t kMfPPGWords = 33;
 // b_k words staged per batch of partial products (mul_ppg_kernel: kMfPPGBatch x 64 LDS words)
 constexpr uint32_t kMfPPGBatch = 8;
 struct MulPPGroup {

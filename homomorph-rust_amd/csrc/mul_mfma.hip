@@ -416,7 +416,9 @@ __device__ __forceinline__ void mf_item(const MulMfmaArgs &P, uint64_t e, uint32
             HM_MF_TAIL(7) HM_MF_TAIL(8) HM_MF_TAIL(9) HM_MF_TAIL(10) HM_MF_TAIL(11) HM_MF_TAIL(12)
             HM_MF_TAIL(13) HM_MF_TAIL(14) HM_MF_TAIL(15) HM_MF_TAIL(16) HM_MF_TAIL(17)
 #undef HM_MF_TAIL
-        default: break;
+        default: // (only past the class bound flagged above: no tail group of this size)
+            if (lane == 0) flag(P.B.status, HM_ERR_BAD_INPUT);
+            break;
         }
 #ifdef HM_MF_PROFILE
         HM_MF_PT(tpc);
@@ -472,7 +474,7 @@ mul_mfma_kernel(MulMfmaArgs P) {
 }
 
 // Partial products a_j * b_k grouped by a_j (MulPPGroup): one wave per (value, group).  a_j has
-// at most kMfPPGWords words, so its chunks (nu/2 + 1 <= 17) are one group: the A fragments are
+// at most kMfPPGWords = 33 words, so its chunks (nu/2 + 1 <= 17) are one group: the A fragments are
 // built once, then every product of the group gets its V image, its tiles (the whole output:
 // span tiles) and its output words and degree.  Same products as mul_mfma_kernel<false>.
 // A product is only 2 x (nu/2 + 1) MFMAs, so its loads are staged per batch of kPPGBatch items
@@ -481,6 +483,7 @@ mul_mfma_kernel(MulMfmaArgs P) {
 // together) -- three dependent loads per batch where a product at a time took three each.
 constexpr int kPPGBatch = (int)kMfPPGBatch;
 static_assert(kMfPPGWords <= 64, "one word per lane");
+static_assert(kMfPPGWords / 2 + 1 <= kMfG + 1, "a_j's chunks are one group: HM_PPG(1..17)");
 
 template <int G, bool PAIRS>
 __device__ __forceinline__ void ppg_products(const MulPPGArgs &P, uint64_t e, const MulPPGroup &grp,
@@ -598,7 +601,9 @@ mul_ppg_kernel(MulPPGArgs P) {
         HM_PPG(1) HM_PPG(2) HM_PPG(3) HM_PPG(4) HM_PPG(5) HM_PPG(6) HM_PPG(7) HM_PPG(8) HM_PPG(9)
         HM_PPG(10) HM_PPG(11) HM_PPG(12) HM_PPG(13) HM_PPG(14) HM_PPG(15) HM_PPG(16) HM_PPG(17)
 #undef HM_PPG
-    default: break;
+    default: // (no instance for this chunk count: never a silent drop of the group's products)
+        if (lane == 0) flag(P.B.status, HM_ERR_BAD_INPUT);
+        break;
     }
 }
 

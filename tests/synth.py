@@ -329,6 +329,68 @@ MUL_CASES = {
     "u16_low4_per_bit": _mul_per_bit(16, SEED + 12) + (False, 4, 8, 2),
 }
 
+def _mc(ba, bb, k=4, signed=False, ka=None):
+    """One multiplier class case: u8 operands (an int: that bound on all 8 bits), mul_low(k) or the
+    full circuit (k None), Karatsuba options ka = (min words, leaf words) or the defaults."""
+    ba = uniform(8, ba) if np.isscalar(ba) else u32(ba)
+    bb = uniform(8, bb) if np.isscalar(bb) else u32(bb)
+    return dict(ba=ba, bb=bb, k=k, signed=signed, ka=ka)
+
+
+# One case per product class of the multiplier at its size edges (DESIGN.md s6): 8 scheduled
+# values + 2 FULL / bound - 1 pairs each; the path of each is asserted from the planner's own
+# census (mul_census) in check_mul_class_path.
+MUL_CLASS_CASES = {
+    "ppv_12w": _mc(383, 383),
+    "ppg_tiny_13w": _mc(384, 384),
+    "ppg_tiny_20w": _mc(639, 639),
+    "ppg_gen_21w": _mc(640, 640),
+    "ppg_gen_33w": _mc(1055, 1055),
+    "w34_1056": _mc(1056, 1056),
+    "w34_1087": _mc(1087, 1087),
+    "ppm_35w": _mc(1088, 1088),
+    "wide_76": _mc(1152, 1152),
+    "ppm_wide": _mc(2304, 2304, k=3),
+    "ppm_narrow_2303": _mc(2303, 2303, k=3),
+    "rows_v36": _mc(287, 287),
+    "tiny_v40": _mc(288, 288),
+    "tiny_v40_319": _mc(319, 319),
+    "narrow_24": _mc(320, 320),
+    "ppg_lopsided": _mc(127, 1055),
+    "ppg_lopsided_swapped": _mc(1055, 127),
+    "tiny_under_wide_prefix": _mc([1200] + [100] * 7, 100),
+    "u8_b640_full": _mc(640, 640, k=None),
+    "i8_b640_full": _mc(640, 640, k=None, signed=True),
+    "u8_b703_ka224": _mc(703, 703, k=None, ka=(224, 224)),
+}
+
+# Degree ladders (ladder): name -> (uniform bound, W values); mul_low(3), so that column 1 pushes
+# exactly one carry product, U = a_0 b_1 against V = a_1 b_0.
+MUL_LADDERS = {
+    "ladder_ppv": (383, 12),
+    "ladder_ppg_tiny": (639, 20),
+    "ladder_ppg_gen": (1055, 33),
+    "ladder_w34": (1087, 34),
+    "ladder_ppm": (1088, 35),
+    "ladder_rows": (287, 9),
+}
+for _n, (_b, _w) in MUL_LADDERS.items():
+    MUL_CLASS_CASES[_n] = _mc(_b, _b, k=3)
+
+
+def ladder(ba, bb, W, seed):
+    """W values; every a_i of value e has exactly e + 1 words: degree 32 (e + 1) - 1 on even bits
+    (the top bit is its word's last; capped at the bound) and 32 e on odd bits (its word's first:
+    value 0's odd bits are the unit polynomial), random below the top bit.  Every b_i is FULL."""
+    rng = np.random.default_rng(seed)
+    A, B = [], []
+    for e in range(W):
+        A.append([_exact(rng, min(32 * (e + 1) - 1, int(b)) if i % 2 == 0 else 32 * e)
+                  for i, b in enumerate(ba)])
+        B.append([_exact(rng, int(b)) for b in bb])
+    return A, B
+
+
 DEC_CASES = {
     # name: per-bit bounds (u8, n = 64)
     "b511_ucap": uniform(8, 511),
@@ -355,12 +417,18 @@ def inputs(family, name):
         ba, bb, ns, npair = ADD_CASES[name]
     elif family == "mul":
         ba, bb, _, _, ns, npair = MUL_CASES[name]
+    elif family == "mulc":
+        ba, bb = MUL_CLASS_CASES[name]["ba"], MUL_CLASS_CASES[name]["bb"]
+        ns, npair = 8, 2
     elif family == "dec":
         ba = bb = DEC_CASES[name]
         ns, npair = DEC_N, 0
     else:
         raise KeyError(family)
-    A, B = batch(ba, bb, ns, npair, _seed(family, name))
+    if family == "mulc" and name in MUL_LADDERS:
+        A, B = ladder(ba, bb, MUL_LADDERS[name][1], _seed(family, name))
+    else:
+        A, B = batch(ba, bb, ns, npair, _seed(family, name))
     return dict(ba=u32(ba), bb=u32(bb), A=A, B=B, n=len(A), nbits=len(ba))
 
 
@@ -415,6 +483,60 @@ def mul_reference(name):
     ob = mul_bounds(c["ba"][:k], c["bb"][:k])
     vals = [mul_ref(a[:k], b[:k], signed) for a, b in zip(c["A"], c["B"])]
     return (ob, vals) + _frozen(*bm.pack(vals, ob))
+
+
+@functools.lru_cache(maxsize=None)
+def mul_class_reference(name):
+    """(out bounds, values, limbs, degree words) of the model's carry-save circuit on a
+    MUL_CLASS_CASES case: the k-bit circuit on the low k bits, or the full (signed) one."""
+    c = inputs("mulc", name)
+    spec = MUL_CLASS_CASES[name]
+    k = spec["k"] or c["nbits"]
+    ob = mul_bounds(c["ba"][:k], c["bb"][:k])
+    vals = [mul_ref(a[:k], b[:k], spec["signed"]) for a, b in zip(c["A"], c["B"])]
+    return (ob, vals) + _frozen(*bm.pack(vals, ob))
+
+
+# ------------------------------------------------------------------ the planner's census
+@functools.lru_cache(maxsize=None)
+def _census_driver():
+    """Builds tests/sanitize/_build/plan_census (the planner compiled into a host-only driver,
+    ASan + UBSan) once per process."""
+    import os
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    subprocess.run(["make", "-s", "-C", os.path.join(root, "homomorph-rust_amd")], check=True,
+                   timeout=1200)
+    san = os.path.join(root, "tests", "sanitize")
+    subprocess.run(["make", "-s", "-C", san, "_build/plan_census"], check=True, timeout=1200)
+    return os.path.join(san, "_build", "plan_census")
+
+
+@functools.lru_cache(maxsize=None)
+def plan_census(L, K, signed, ka_min, ka_leaf, mfma, ba, bb):
+    """The planner's own account of one plan (tests/sanitize/plan_census.cpp), as a dict.  CPU
+    only.  Any sanitizer report fails the run."""
+    import json
+    import os
+    import subprocess
+    args = [L, K, int(signed), ka_min, ka_leaf, int(mfma)] + list(ba) + list(bb)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0",
+               UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([_census_driver()] + [str(int(x)) for x in args], capture_output=True,
+                       text=True, timeout=300, env=env)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    return json.loads(r.stdout)
+
+
+def mul_census(name, mfma=True):
+    """The census of a MUL_CLASS_CASES case as mul_columns plans it: L = 8, K = k, the signed
+    corners only in the full circuit (mul_host.cpp mul_columns: flip = is_signed && K == L), the
+    context's Karatsuba defaults (ctx.h: 256, 256) unless the case sets its own."""
+    spec = MUL_CLASS_CASES[name]
+    K = spec["k"] or 8
+    ka = spec["ka"] or (256, 256)
+    return plan_census(8, K, spec["signed"] and K == 8, ka[0], ka[1], mfma,
+                       tuple(int(x) for x in spec["ba"][:K]), tuple(int(x) for x in spec["bb"][:K]))
 
 
 @functools.lru_cache(maxsize=None)
@@ -540,6 +662,152 @@ def check_mul_path(name):
     if "per_bit" in name:
         assert len(set(caps.tolist())) >= 2 and (c["ba"] // 64 != c["bb"] // 64).any()
     return dict(caps=caps)
+
+
+def _launch(m, instance, umax, vmax=None):
+    return (m["nspans"] > 0 and m["instance"] == instance and m["umax"] == umax
+            and (vmax is None or m["vmax"] == vmax))
+
+
+def check_mul_class_path(name):
+    """The path each MUL_CLASS_CASES case is named for, from the planner's census of the case's
+    bounds (mul_census: which launch mul_columns makes, with which sizes, and the instance
+    launch_mul_ppg / launch_mul_mfma pick for it) together with the model's integers (the word
+    counts the kernels then branch on: nu = words(a_j) in mul_ppv_kernel / mul_ppg_kernel, nu / 2
+    + 1 chunks in one group there, groups of 16 and one tail group of 1..17 in mf_item)."""
+    c = inputs("mulc", name)
+    spec = MUL_CLASS_CASES[name]
+    K = spec["k"] or 8
+    cen = mul_census(name)
+    cols = cen["cols"]
+    TINY, NARROW, WIDE = 0, 1, 2
+    assert len(cols) == K
+    # VALU plans keep every product off the matrix cores
+    valu = mul_census(name, mfma=False)
+    assert not valu["ppg"] and not valu["ppv"]
+    assert all(not col["ppl"]["nspans"] and not col["nrows"] and
+               not any(m["nspans"] for m in col["mfl"]) for col in valu["cols"])
+    nua = [[words(v[j]) for j in range(K)] for v in c["A"]]     # per value: words of a_j
+    nub = [[words(v[j]) for j in range(K)] for v in c["B"]]
+    if name not in MUL_LADDERS:
+        # some value fills every operand slot the plan sized (the FULL / bound - 1 pairs)
+        for j in range(K):
+            assert max(r[j] for r in nua) == int(c["ba"][j]) // 32 + 1
+            assert max(r[j] for r in nub) == int(c["bb"][j]) // 32 + 1
+        # ... and the schedule puts a null and a unit operand in every bit position
+        for X in (c["A"], c["B"]):
+            for j in range(K):
+                assert {0, 1} <= {X[e][j] for e in range(8)}
+    ppl = [col["ppl"] for col in cols]
+    pp = cen["pp_instance"]
+    if name == "ppv_12w":
+        assert cen["ppg"] and cen["ppv"] and cen["ppg_umax"] == 12 and pp == "mul_ppv_kernel"
+    elif name in ("ppg_tiny_13w", "ppg_tiny_20w"):
+        assert cen["ppg"] and not cen["ppv"] and pp == "mul_ppg_kernel<11>"
+        assert cen["ppg_umax"] == {"ppg_tiny_13w": 13, "ppg_tiny_20w": 20}[name]
+    elif name in ("ppg_gen_21w", "ppg_gen_33w"):
+        assert cen["ppg"] and not cen["ppv"] and pp == "mul_ppg_kernel<17>"
+        assert cen["ppg_umax"] == {"ppg_gen_21w": 21, "ppg_gen_33w": 33}[name]
+        if name == "ppg_gen_21w":
+            assert _launch(cols[1]["mfl"][NARROW], "narrow", 44)
+        else:  # 33 words: 17 chunks, the last count mul_ppg_kernel's one group holds
+            assert max(r[0] for r in nua) // 2 + 1 == 17
+    elif name in ("w34_1056", "w34_1087", "ppm_35w"):
+        # 34 words are 18 chunks, one more than mul_ppg_kernel's group: no grouped launch
+        # (kMfPPGWords = 33), the partial products are per-column launches on the narrow instance
+        assert not cen["ppg"] and not cen["ppv"] and pp == ""
+        assert all(_launch(m, "narrow", 36, 36) for m in ppl)
+        assert max(r[0] for r in nua) == (35 if name == "ppm_35w" else 34)
+        u = 72 if name == "ppm_35w" else 68
+        assert _launch(cols[1]["mfl"][NARROW], "narrow", u) and _launch(cols[2]["mfl"][NARROW], "narrow", u)
+        assert not any(col["mfl"][WIDE]["nspans"] for col in cols)
+    elif name == "wide_76":
+        assert all(_launch(m, "narrow", 40, 40) for m in ppl)
+        assert _launch(cols[1]["mfl"][WIDE], "wide_win", 76) and _launch(cols[2]["mfl"][WIDE], "wide_win", 76)
+        assert not any(col["mfl"][NARROW]["nspans"] for col in cols)
+    elif name == "ppm_wide":
+        assert not cen["ppg"] and all(_launch(m, "wide", 76, 76) for m in ppl)
+    elif name == "ppm_narrow_2303":
+        assert not cen["ppg"] and all(_launch(m, "narrow", 72, 72) for m in ppl)
+    elif name == "rows_v36":
+        col = cols[2]
+        assert (col["nrows"], col["rows_uw"], col["rows_vw"], col["rows_qw"]) == (3, 20, 36, 18)
+        assert not any(m["nspans"] for col in cols for m in col["mfl"])
+    elif name in ("tiny_v40", "tiny_v40_319"):
+        col = cols[2]
+        assert _launch(col["mfl"][TINY], "tiny", 20, 40) and col["mfl"][TINY]["nspans"] == 1
+        assert col["nrows"] == 2 and col["rows_qw"] == (19 if name == "tiny_v40" else 20)
+    elif name == "narrow_24":
+        assert not any(col["nrows"] for col in cols)
+        assert _launch(cols[1]["mfl"][NARROW], "narrow", 24) and _launch(cols[2]["mfl"][NARROW], "narrow", 24)
+    elif name == "ppg_lopsided":
+        assert (cen["ppg_umax"], cen["ppg_vmax"], pp) == (4, 33, "mul_ppg_kernel<11>")
+    elif name == "ppg_lopsided_swapped":
+        assert (cen["ppg_umax"], cen["ppg_vmax"], pp) == (33, 4, "mul_ppg_kernel<17>")
+    elif name == "tiny_under_wide_prefix":
+        assert not cen["ppg"] and all(_launch(m, "tiny", 4, 40) for m in ppl)
+        assert _launch(cols[1]["mfl"][TINY], "tiny", 8, 44) and _launch(cols[2]["mfl"][TINY], "tiny", 8, 44)
+    elif name in ("u8_b640_full", "i8_b640_full"):
+        assert pp == "mul_ppg_kernel<17>" and cen["ppg_umax"] == 21
+        for i in (3, 4, 5, 6):
+            assert cols[i]["mfl"][NARROW]["instance"] == "narrow"
+            assert cols[i]["mfl"][WIDE]["instance"] == "wide_win"
+        ka = cols[6]["ka"]
+        assert len(ka) == 4 and {g["lane"] for g in ka} == {0, 1}
+        assert {g["leaf_umax"] for g in ka} == {192, 256} and not any(g["lean_leaf"] for g in ka)
+        # the signed corners: two VALU partial products (+1) in column 7, beside the grouped launch
+        assert [col["npp"] for col in cols] == [0] * 7 + [2 if spec["signed"] else 0]
+        assert bool(cen["signed"]) == spec["signed"]
+    elif name == "u8_b703_ka224":
+        lean = [g for col in cols for g in col["ka"] if g["lean_leaf"]]
+        assert {g["lane"] for g in lean} == {0, 1}
+        assert all(g["leaf_umax"] == 224 and g["leaf_vmax"] == 224 for g in lean)
+    elif name in MUL_LADDERS:
+        _check_ladder(name, c, cen, nua)
+    else:
+        raise KeyError(name)
+    return cen
+
+
+def _check_ladder(name, c, cen, nua):
+    B, W = MUL_LADDERS[name]
+    cols = cen["cols"]
+    assert c["n"] == W
+    for e in range(W):  # exactly e + 1 words; tops on a word's last bit (even) / first bit (odd)
+        assert set(nua[e]) == {e + 1}
+        assert c["A"][e][0].bit_length() == min(32 * (e + 1), B + 1)
+        assert c["A"][e][1].bit_length() == 32 * e + 1
+        assert all(b.bit_length() - 1 == B for b in c["B"][e])
+    nu = [r[0] for r in nua]
+    chunks = [n // 2 + 1 for n in nu]
+    # column 1's carry product: U = p_1 = a_0 b_1 (the prefix; both slots have equal capacity, and
+    # mul_host.cpp takes the prefix as U then)
+    u1 = [words(model.clmul_fast(a[0], b[1])) for a, b in zip(c["A"], c["B"])]
+    if name == "ladder_ppv":
+        assert cen["pp_instance"] == "mul_ppv_kernel" and cen["ppg_umax"] == 12
+        assert nu == list(range(1, 13))
+    elif name == "ladder_ppg_tiny":
+        assert cen["pp_instance"] == "mul_ppg_kernel<11>" and cen["ppg_umax"] == 20
+        assert set(chunks) == set(range(1, 12))
+    elif name == "ladder_ppg_gen":
+        assert cen["pp_instance"] == "mul_ppg_kernel<17>" and cen["ppg_umax"] == 33
+        assert set(chunks) == set(range(1, 18))
+        assert _launch(cols[1]["mfl"][1], "narrow", 68) and u1 == list(range(34, 67))
+    elif name in ("ladder_w34", "ladder_ppm"):
+        # per-column launches on the narrow instance: chunk counts 1..18, so every tail group
+        # 1..17 and, at 18, one full group of 16 and a tail of 2
+        assert not cen["ppg"] and all(_launch(col["ppl"], "narrow", 36, 36) for col in cols)
+        assert set(chunks) == set(range(1, 19)) and chunks[-1] == 18
+        # the carry's U on the narrow instance at every word count 35..68: chunk counts 18..35,
+        # every tail size after one full group and after two
+        assert _launch(cols[1]["mfl"][1], "narrow", 68 if name == "ladder_w34" else 72)
+        assert u1[:34] == list(range(35, 69))
+        assert {n // 2 + 1 for n in u1[:34]} == set(range(18, 36))
+    elif name == "ladder_rows":
+        col = cols[1]
+        assert (col["nrows"], col["rows_uw"], col["rows_qw"]) == (1, 20, 18)
+        # deg U = deg a_0 + 287: 10 words at value 0, rows_qw = 18 at the last
+        assert u1 == list(range(10, 19))
 
 
 def check_dec_path(name):

@@ -263,6 +263,74 @@ def test_mul(H, world, name, products):
     same(out, ob, rl, rd, c["n"], f"{name}/{products}")
 
 
+@pytest.mark.parametrize("products", ["mfma", "valu"])
+@pytest.mark.parametrize("name", list(synth.MUL_CLASS_CASES))
+def test_mul_classes(H, world, name, products):
+    """Every product class of the multiplier at its size edges, and the degree ladders that walk
+    the kernels' inner paths.  build_plan (mul_host.cpp) picks the launches from the static
+    bounds; the kernels pick their path from each operand's word count nu (from its degree).
+    u8 operands, uniform bounds a / b unless noted, mul_low(4) unless noted; paths from the
+    planner's own census (synth.check_mul_class_path, test_synth_reference.py):
+      ppv_12w        383          `P.ppv = max(ppg_umax, ppg_vmax) <= kPPVWords`: 12 words, the last
+      ppg_tiny_13w   384          grouped launch; launch_mul_ppg `a.umax <= kMfTinyWords`:
+      ppg_tiny_20w   639          mul_ppg_kernel<11> at its first and last size
+      ppg_gen_21w    640          mul_ppg_kernel<kMfG + 1>, first size; narrow carries U = 44
+      ppg_gen_33w    1055         33 words = 17 chunks, the last `max(wa, wb) <= kMfPPGWords`
+      w34_1056, w34_1087          34 words = 18 chunks, one more than mul_ppg_kernel's `switch
+                                  (nu / 2 + 1)` has: per-column launches (ppm, umax 36) since
+                                  kMfPPGWords = 33; carries narrow at U = 68
+      ppm_35w        1088         ppm umax 36 on the narrow instance; carries narrow at U = 72 =
+                                  kMfNarrowWords, the class's last size
+      wide_76        1152         `uw <= kMfNarrowWords ? 1 : 2`: carries wide (windowed,
+                                  mul_mfma_kernel<false, true, true>) at U = 76, its first size
+      ppm_wide       2304, k = 3  ppm umax 76: launch_mul_mfma's last branch, mul_mfma_kernel<false>
+      ppm_narrow_2303  2303, k = 3  ... and umax 72 beside it, narrow
+      rows_v36       287          rows_ok `uw <= kRowsU && vw <= kRowsV`: column 2 has 3 row
+                                  products, rows_uw 20, rows_vw 36, rows_qw 18
+      tiny_v40       288, 319     column 2's third product has V = 40 > kRowsV: one span on the tiny
+                                  MFMA instance (U = 20), rows_qw 19 and 20 beside it
+      narrow_24      320          U = 24 > kRowsU: no rows, narrow
+      ppg_lopsided   127 / 1055   ppg_umax 4 against ppg_vmax 33 on mul_ppg_kernel<11>, and swapped
+                                  (33 against 4, mul_ppg_kernel<17>)
+      tiny_under_wide_prefix  a = [1200, 100, ..], b = 100: ppm umax 4 / vmax 40 on the tiny
+                                  instance, tiny carries U = 8, V = 44
+      u8_b640_full, i8_b640_full  640, the full circuit: general ppg, narrow + wide launches in
+                                  columns 3..6, four Karatsuba programs on both lanes in column 6
+                                  (leaves 192 and 256, mul_mfma_kernel<true>); signed: the two
+                                  flipped VALU partial products of column 7 beside the ppg launch
+      u8_b703_ka224  703, full, set_mul_options(224, 224): 224-word leaves on both lanes on the
+                                  lean leaf instance (run_ka: `a.umax <= kMfLeanLeafWords &&
+                                  a.umax >= kMfLeanLeafMin`, mul_mfma_kernel<true, true>)
+    Ladders (synth.ladder: value e's a_i has e + 1 words, b FULL, mul_low(3), one carry product
+    U = a_0 b_1 in column 1):
+      ladder_ppv 383 x 12      nu = 1..12 in mul_ppv_kernel's rows
+      ladder_ppg_tiny 639 x 20 `switch (nu / 2 + 1)`: 1..11
+      ladder_ppg_gen 1055 x 33 ... 1..17; the narrow carry's U at 34..66 words
+      ladder_w34 1087 x 34, ladder_ppm 1088 x 35   mf_item's groups through ppm: 1..18 chunks (every
+                               tail 1..17, then 16 + 2); the narrow carry's U at 35..68 words: 18..35
+                               chunks, every tail after one full group and after two
+      ladder_rows 287 x 9      mul_rows_kernel's U at 10..18 words against rows_qw = 18
+    "valu" runs the same cases with every product off the matrix cores.  Bit-exact against
+    gf2_model.mul_circuit (limbs, degree words, out.bound)."""
+    ctx = world()
+    c, a, b = upload(H, ctx, "mulc", name)
+    spec = synth.MUL_CLASS_CASES[name]
+    ctx.set_mul_products(products)
+    if spec["ka"]:
+        ctx.set_mul_options(*spec["ka"])
+    try:
+        if spec["k"]:
+            out = ctx.mul_low(a, b, spec["k"])
+        else:
+            out = ctx.apply2(H.HomomorphicMultiplication, a, b, signed=spec["signed"])
+        ctx.synchronize()
+    finally:
+        ctx.set_mul_products("auto")
+        ctx.set_mul_options()
+    ob, _, rl, rd = synth.mul_class_reference(name)
+    same(out, ob, rl, rd, c["n"], f"{name}/{products}")
+
+
 # ------------------------------------------------------------------ decryption
 @pytest.mark.parametrize("name", list(synth.DEC_CASES))
 def test_decrypt(H, world, oracle, name):

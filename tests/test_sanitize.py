@@ -8,6 +8,8 @@ engine library's host code, run on the CPU (GPU sanitizers are not available on 
   contexts), with the device kernels linked in unsanitised;
 - tests/sanitize/plan_split.cpp: the multiplier planner's split Karatsuba plans (host only): the
   same leaf products as the breadth-first plans at K = 16, K = 21 planned;
+- tests/sanitize/plan_census.cpp: one plan's launches and sizes as JSON (host only), the source of
+  the full-bounds tier's multiplier path assertions (tests/synth.py mul_census);
 - tests/sanitize/capi_oom.cpp (not sanitised): every allocation inside the multiplier's plan
   builder failed in turn, each call returning HM_ERR_OUT_OF_MEMORY instead of throwing across
   the C ABI.
@@ -56,3 +58,21 @@ def test_engine_abi_returns_oom_instead_of_throwing(built):
 
 def test_split_karatsuba_plans_under_asan_ubsan(built):
     assert "ok" in _run(os.path.join(built, "plan_split"))
+
+
+def test_plan_census_under_asan_ubsan(built):
+    """tests/sanitize/plan_census.cpp (the driver behind synth.mul_census): the full signed u8
+    plan at bounds 640 with its Karatsuba programs, and a refused argument list."""
+    import json
+    exe = os.path.join(built, "plan_census")
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0",
+               UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe, "8", "8", "1", "256", "256", "1"] + ["640"] * 16, capture_output=True,
+                       text=True, timeout=300, env=env)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    cen = json.loads(r.stdout)
+    assert len(cen["cols"]) == 8 and cen["pp_instance"] == "mul_ppg_kernel<17>"
+    assert sum(len(col["ka"]) for col in cen["cols"]) == 5
+    r = subprocess.run([exe, "8", "4", "0", "256", "256", "1", "640"], capture_output=True,
+                       text=True, timeout=300, env=env)
+    assert r.returncode == 2 and "expected" in r.stderr

@@ -165,6 +165,34 @@ def test_mul_reference(H, oracle, name):
     synth.check_mul_path(name)
 
 
+@pytest.mark.parametrize("name", list(synth.MUL_CLASS_CASES))
+def test_mul_class_reference(H, oracle, name):
+    """The multiplier's product classes at their size edges and the degree ladders: the case's
+    path from the planner's census (synth.check_mul_class_path), every output degree within
+    hm_mul_out_bounds, and the model pinned to the bit-serial oracle on the first two values and
+    the last one (a ladder's widest)."""
+    from helpers import low_bits
+    c = synth.inputs("mulc", name)
+    spec = synth.MUL_CLASS_CASES[name]
+    k, signed = spec["k"], spec["signed"]
+    ob, vals, rl, rd = synth.mul_class_reference(name)
+    nbits = k or c["nbits"]
+    assert np.array_equal(ob, H.mul_out_bounds(c["ba"][:nbits], c["bb"][:nbits], signed))
+    cen = synth.check_mul_class_path(name)
+    assert [col["res_bound"] for col in cen["cols"]] == ob.tolist()
+    within(vals, ob)
+    pick = sorted({0, 1, c["n"] - 1})
+    la, da = bm.pack([c["A"][e] for e in pick], c["ba"])
+    lb, db = bm.pack([c["B"][e] for e in pick], c["bb"])
+    ba, bb = c["ba"], c["bb"]
+    if k:
+        la, da, ba = low_bits(la, da, ba, len(pick), k)
+        lb, db, bb = low_bits(lb, db, bb, len(pick), k)
+    ol, od = oracle.mul_batch(la, da, ba, lb, db, bb, nbits, len(pick), ob, signed=signed)
+    ml, md = bm.pack([vals[e] for e in pick], ob)
+    assert_batches_equal(ml, md, ol, od, ob, len(pick), name)
+
+
 # ------------------------------------------------------------------ decryption
 @pytest.mark.parametrize("name", list(synth.DEC_CASES))
 def test_dec_reference(oracle, name):
