@@ -49,8 +49,12 @@ namespace hm {
 
 // Phase timers (tools/chain_check.hip builds with HM_MFMA_PROFILE; the library never does):
 // per-wave sums of s_memtime deltas for the sum store, the A build and the tile loop.
+// With them, per wave: s_memrealtime at entry and at the end (100 MHz, one clock for the whole
+// device: the waves' finish times are comparable across SIMDs and XCDs), the wave's life in
+// s_memtime ticks, and where it ran (HW_ID, XCC_ID).
 #ifdef HM_MFMA_PROFILE
-__device__ unsigned long long *g_mfma_prof; // 4 per wave, set by the harness
+constexpr int kMfmaProfSlots = 8; // [0..3] phase sums, [4] start, [5] end, [6] life, [7] XCC_ID << 32 | HW_ID
+__device__ unsigned long long *g_mfma_prof; // kMfmaProfSlots per wave, set by the harness
 #define HM_PT(v) const unsigned long long v = __builtin_amdgcn_s_memtime()
 #define HM_PACC(k, a, b) prof[k] += (b) - (a)
 #else
@@ -146,6 +150,35 @@ __device__ __forceinline__ void sum_store(uint64_t base, uint32_t off, uint32_t 
     asm volatile("global_store_dword %0, %1, %2" : : "v"(off), "v"(v), "s"(base) : "memory");
 }
 
+// s_getreg_b32 operands: register id | first bit << 6 | (bits - 1) << 11
+constexpr int kGetregHwId = 4 | 31 << 11;         // HW_REG_HW_ID: wave slot [3:0], SIMD [5:4], CU [11:8], SH [12], SE [15:13]
+constexpr int kGetregWaveSlot = 4 | 3 << 11;      // its WAVE_ID field
+constexpr int kGetregXccId = 20 | 3 << 11;        // HW_REG_XCC_ID [3:0]
+
+// The priority of a SIMD's chain waves (DESIGN.md 4.1 "The four waves of a SIMD"):
+//   0  level 1 for every wave's MFMA phase, 0 between them.  The arbiter breaks the tie by age:
+//      the oldest wave runs ahead and the SIMD ends the kernel with three, two, one wave
+//      (chain_check: the four finish at 0.63 / 0.74 / 0.87 / 0.97 of the kernel);
+//   2  level (slot + i) % 4 held for the whole of bit i (slot: the wave's slot on its SIMD, read
+//      once): no wave stays the favourite, the four finish at 0.87 / 0.89 / 0.93 / 0.95 and the
+//      kernel is 2-3 % shorter.  Scalar only: a wave chooses its own level and waits for nobody.
+// (1, levels 1 + (slot + i) % 3 around the MFMA phases only, measured in between and was removed.)
+// The 13-chunk instance takes the knob.  The other two keep 0: their measured launches are many
+// rounds of waves, where a finished wave's place is taken at once and the rotation only costs
+// (configs[0]'s u8 chain 288-291 -> 291-294 us, configs[4]'s add chunk 47.1-47.4 -> 47.4-47.5 ms).
+#ifndef HM_CHAIN_PRIO
+#define HM_CHAIN_PRIO 2
+#endif
+static_assert(HM_CHAIN_PRIO == 0 || HM_CHAIN_PRIO == 2, "HM_CHAIN_PRIO: 0 (by age) or 2 (rotating levels)");
+template <int NC> constexpr int kChainPrio = NC == 13 ? HM_CHAIN_PRIO : 0;
+// s_setprio takes an immediate: a wave-uniform level (an SGPR) selects one by scalar branches
+__device__ __forceinline__ void set_prio(uint32_t level) {
+    if (level == 0) __builtin_amdgcn_s_setprio(0);
+    else if (level == 1) __builtin_amdgcn_s_setprio(1);
+    else if (level == 2) __builtin_amdgcn_s_setprio(2);
+    else __builtin_amdgcn_s_setprio(3);
+}
+
 // waves per block (<= kAddWavesPerBlock, which the host plan's LDS check assumes)
 #ifndef HM_MFMA_WPB
 #define HM_MFMA_WPB kAddWavesPerBlock
@@ -160,6 +193,10 @@ template <int NC>
 __global__ void __launch_bounds__(64 * kMfmaWpb)
 __attribute__((amdgpu_waves_per_eu(MfmaCfg<NC>::kWavesPerEU, MfmaCfg<NC>::kWavesPerEU)))
 add_chain_mfma_kernel(AddArgs A) {
+#ifdef HM_MFMA_PROFILE
+    const unsigned long long prof_rt0 = __builtin_amdgcn_s_memrealtime();
+    const unsigned long long prof_st0 = __builtin_amdgcn_s_memtime();
+#endif
     kt_start(A.kt);
     using Cfg = MfmaCfg<NC>;
     constexpr int kRevWords = Cfg::kRevWords, kRsWords = Cfg::kRsWords, kRec = Cfg::kRecWords;
@@ -227,6 +264,9 @@ add_chain_mfma_kernel(AddArgs A) {
         }
     };
     stage_rec(0);
+    constexpr int kPrio = kChainPrio<NC>;
+    uint32_t slot = 0u;
+    if constexpr (kPrio == 2) slot = __builtin_amdgcn_s_getreg(kGetregWaveSlot); // (an SGPR, read once)
 
 #ifdef HM_MFMA_PROFILE
     unsigned long long prof[4] = {0, 0, 0, 0};
@@ -241,6 +281,7 @@ add_chain_mfma_kernel(AddArgs A) {
     uint32_t offo = 0;
     for (uint32_t i = 0; i < L; ++i) {
         HM_PT(tw0);
+        if constexpr (kPrio == 2) set_prio((slot + i) & 3u); // this bit's level, tiles and tail alike
         wait_record(young); // bit i's record has landed
         young = 0;
         const uint32_t *rec = &stage[wave][i & 1][0];
@@ -411,7 +452,7 @@ add_chain_mfma_kernel(AddArgs A) {
                 const int W = 32 * T + (lane_opaque() & 31); // (built here: not a per-tile value)
                 abw = W < nab ? abi[W] : 0u;
             }
-            __builtin_amdgcn_s_setprio(1); // the MFMA phase keeps the pipe
+            if constexpr (kPrio == 0) __builtin_amdgcn_s_setprio(1); // the MFMA phase keeps the pipe
             acc = tile_mfma<NC>(Af, rb, rbn, pf, acc, [&](int stage) {
                 // (the empty asm keep each stage's arithmetic from being hoisted into an earlier
                 // stage, where it would wait for the read of the stage before)
@@ -428,7 +469,7 @@ add_chain_mfma_kernel(AddArgs A) {
                     if (mirror) *lds_at<u32x2>(pp + 16u * kMfmaRingSlots) = fn;
                 }
             });
-            __builtin_amdgcn_s_setprio(0);
+            if constexpr (kPrio == 0) __builtin_amdgcn_s_setprio(0);
             // accumulator j of lane half h is output bit j + 16h (row-permuted tiles): its parity
             // is bit 16 + j of tnow; XOR the bits of the accumulators before this tile
             const uint32_t tnow = acc_parities_hi16(acc);
@@ -479,8 +520,13 @@ add_chain_mfma_kernel(AddArgs A) {
         HM_PACC(2, t2, t3);
     }
 #ifdef HM_MFMA_PROFILE
-    if (lane == 0)
-        for (int k = 0; k < 4; ++k) g_mfma_prof[e * 4 + k] = prof[k];
+    if (lane == 0) {
+        unsigned long long *g = g_mfma_prof + e * kMfmaProfSlots;
+        for (int k = 0; k < 4; ++k) g[k] = prof[k];
+        g[4] = prof_rt0, g[5] = __builtin_amdgcn_s_memrealtime();
+        g[6] = __builtin_amdgcn_s_memtime() - prof_st0;
+        g[7] = (unsigned long long)__builtin_amdgcn_s_getreg(kGetregXccId) << 32 | __builtin_amdgcn_s_getreg(kGetregHwId);
+    }
 #endif
     kt_finish(A.kt);
 }

@@ -9,9 +9,12 @@
 #endif
 #include "../homomorph-rust_amd/csrc/adder_mfma.hip"
 
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <random>
 #include <vector>
 
@@ -130,7 +133,7 @@ static int run_case(int L, int npw, int abw, int mode, int pbit, int cbit, bool 
 #ifdef HM_MFMA_PROFILE
     static unsigned long long *dprof1 = nullptr;
     if (!dprof1) {
-        hipMalloc(&dprof1, 64);
+        hipMalloc(&dprof1, kMfmaProfSlots * 8);
         hipMemcpyToSymbol(HIP_SYMBOL(g_mfma_prof), &dprof1, sizeof dprof1);
     }
 #endif
@@ -167,6 +170,78 @@ static int run_case(int L, int npw, int abw, int mode, int pbit, int cbit, bool 
     return bad;
 }
 
+#ifdef HM_MFMA_PROFILE
+// When each wave of the last launch finished, as a fraction of the kernel (earliest entry stamp to
+// latest end stamp, s_memrealtime), grouped by the SIMD it ran on: one "simd" row per (XCC, SE,
+// SH, CU, SIMD) with its waves' slots and sorted finish fractions, then the means over the SIMDs
+// that held four waves.  Every value is the same record, so every wave has the same work:
+// a spread inside a SIMD is the arbiter's, a spread between SIMDs is placement or clocks.
+// scripts/chain_finish.py reads the rows.
+static void finish_table(const std::vector<unsigned long long> &hp, int nvals) {
+    struct Wv { uint32_t slot; double f; };
+    unsigned long long t0 = ~0ull, t1 = 0, s1 = 0;
+    double life = 0;
+    for (int v = 0; v < nvals; ++v) {
+        const unsigned long long *g = &hp[(size_t)v * kMfmaProfSlots];
+        t0 = std::min(t0, g[4]), s1 = std::max(s1, g[4]), t1 = std::max(t1, g[5]);
+        life += (double)g[6] / ((double)(g[5] - g[4]) + 1e-9);
+    }
+    const double span = (double)(t1 - t0);
+    printf("finish: kernel %.2f us (s_memrealtime, 10 ns ticks), entry stamps within %.2f us, shader clock %.0f MHz\n",
+           span / 100, (double)(s1 - t0) / 100, life / nvals * 100);
+    std::map<uint32_t, std::vector<Wv>> simds; // key: XCC << 16 | SE, SH, CU << 4 | SIMD
+    int slots[16] = {};
+    for (int v = 0; v < nvals; ++v) {
+        const unsigned long long *g = &hp[(size_t)v * kMfmaProfSlots];
+        const uint32_t hw = (uint32_t)g[7], xcc = (uint32_t)(g[7] >> 32) & 15u;
+        ++slots[hw & 15u];
+        simds[xcc << 16 | (hw >> 8 & 0xFFu) << 4 | (hw >> 4 & 3u)].push_back({hw & 15u, (double)(g[5] - t0) / span});
+    }
+    printf("finish: wave slots used:");
+    for (int k = 0; k < 16; ++k)
+        if (slots[k]) printf(" %d: %d", k, slots[k]);
+    printf("\n");
+    double rank[4] = {}, all = 0, lastmin = 2, lastmax = 0, last2 = 0, xl[16] = {};
+    int n4 = 0, xn[16] = {};
+    for (auto &[key, w] : simds) {
+        std::sort(w.begin(), w.end(), [](const Wv &a, const Wv &b) { return a.f < b.f; });
+        printf("simd xcc %u se %u sh %u cu %2u simd %u waves %zu slots", key >> 16, key >> 9 & 7u, key >> 8 & 1u,
+               key >> 4 & 15u, key & 3u, w.size());
+        for (auto &x : w) printf(" %u", x.slot);
+        printf(" finish");
+        for (auto &x : w) printf(" %.4f", x.f);
+        printf("\n");
+        if (w.size() != 4) continue;
+        ++n4;
+        for (int r = 0; r < 4; ++r) rank[r] += w[r].f, all += w[r].f;
+        lastmin = std::min(lastmin, w[3].f), lastmax = std::max(lastmax, w[3].f), last2 += w[3].f * w[3].f;
+        xl[key >> 16] += w[3].f, ++xn[key >> 16];
+    }
+    // per XCC: waves, the mean wave's life and phase sums (s_memtime ticks) and its clock
+    double xs[16][7] = {};
+    for (int v = 0; v < nvals; ++v) {
+        const unsigned long long *g = &hp[(size_t)v * kMfmaProfSlots];
+        double *x = xs[(g[7] >> 32) & 15u];
+        x[0] += 1, x[1] += (double)g[6], x[6] += (double)(g[5] - g[4]);
+        for (int k = 0; k < 4; ++k) x[2 + k] += (double)g[k];
+    }
+    for (int x = 0; x < 16; ++x)
+        if (xs[x][0] > 0)
+            printf("xcc %d: %4.0f waves, life %8.0f ticks (%.0f MHz): sum-store %7.0f, RS+A build %7.0f, tiles %8.0f, vmcnt wait %8.0f\n",
+                   x, xs[x][0], xs[x][1] / xs[x][0], xs[x][1] / xs[x][6] * 100, xs[x][2] / xs[x][0], xs[x][3] / xs[x][0],
+                   xs[x][4] / xs[x][0], xs[x][5] / xs[x][0]);
+    if (!n4) return;
+    const double lm = rank[3] / n4;
+    printf("finish: %d SIMDs with four waves (of %zu); mean finish fraction by rank %.4f %.4f %.4f %.4f; of all waves %.4f\n",
+           n4, simds.size(), rank[0] / n4, rank[1] / n4, rank[2] / n4, lm, all / (4.0 * n4));
+    printf("finish: last finisher across SIMDs: min %.4f mean %.4f max %.4f sd %.4f; mean by XCC:", lastmin, lm, lastmax,
+           sqrt(std::max(0.0, last2 / n4 - lm * lm)));
+    for (int x = 0; x < 16; ++x)
+        if (xn[x]) printf(" %d: %.4f", x, xl[x] / xn[x]);
+    printf("\n");
+}
+#endif
+
 // configs[1]-shaped chain (32 bits, P 25 words, ab 17 words, x 9 words; wide: configs[4]'s,
 // P 49, ab 33, x 17) replicated over nvals values: kernel time and per-phase s_memtime sums
 // (cycles summed over waves)
@@ -183,7 +258,11 @@ static int timing(int nvals, bool wide) {
         uint32_t *w = &ws[(size_t)v * A.ws_stride];
         for (int i = 0; i < L; ++i) {
             for (uint32_t k = 0; k < cntAB; ++k) w[i * cntAB + k] = (uint32_t)rng();
-            w[i * cntAB + cntAB - 1] &= 0x7FFFFFFFu;
+            // deg ab_i <= 2 D, as a product of two fresh ciphertexts has: one bit in the top word.
+            // (With more, every sum bit is over its bound and every wave flags HM_ERR_CAPACITY on
+            // the one status word at every bit: 131,072 atomics on one address per launch, which
+            // took the launch from 0.46 to 1.5 ms and spread the XCDs' finish times by 2x.)
+            w[i * cntAB + cntAB - 1] &= 1u;
             for (uint32_t k = 0; k < cntP; ++k) w[L * cntAB + i * cntP + k] = k + 1 < cntP ? (uint32_t)rng() : 1u;
             w[L * (cntAB + cntP) + i] = degp1(&w[i * cntAB], cntAB);
             w[L * (cntAB + cntP) + L + i] = degp1(&w[L * cntAB + i * cntP], cntP);
@@ -218,7 +297,7 @@ static int timing(int nvals, bool wide) {
     hipEventCreate(&e0), hipEventCreate(&e1);
 #ifdef HM_MFMA_PROFILE
     unsigned long long *dprof;
-    hipMalloc(&dprof, (size_t)nvals * 4 * 8);
+    hipMalloc(&dprof, (size_t)nvals * kMfmaProfSlots * 8);
     hipMemcpyToSymbol(HIP_SYMBOL(g_mfma_prof), &dprof, sizeof dprof);
 #endif
     // ~0.3 s of launches first: the clock ramps up under load (MI355X_MICROARCH.md DVFS)
@@ -254,15 +333,19 @@ static int timing(int nvals, bool wide) {
         hipEventSynchronize(e1);
         hipEventElapsedTime(&ms, e0, e1);
     }
+    int st = 0;
+    hipMemcpy(&st, dst, 4, hipMemcpyDeviceToHost);
+    if (st) printf("status %d: the record is outside the plan the timing stands for\n", st);
 #ifdef HM_MFMA_PROFILE
-    std::vector<unsigned long long> hp((size_t)nvals * 4);
+    std::vector<unsigned long long> hp((size_t)nvals * kMfmaProfSlots);
     hipMemcpy(hp.data(), dprof, hp.size() * 8, hipMemcpyDeviceToHost);
     double z[4] = {0, 0, 0, 0};
     for (int v = 0; v < nvals; ++v)
-        for (int k = 0; k < 4; ++k) z[k] += (double)hp[(size_t)v * 4 + k];
+        for (int k = 0; k < 4; ++k) z[k] += (double)hp[(size_t)v * kMfmaProfSlots + k];
     const double waves = (double)nvals; // the last launch's per-wave sums
-    printf("chain %d values: %.1f us per launch; per wave (s_memtime ticks): sum-store %.0f, RS+A build %.0f, tiles %.0f, vmcnt wait %.0f\n",
-           nvals, ms * 1e3 / reps, z[0] / waves, z[1] / waves, z[2] / waves, z[3] / waves);
+    printf("chain %d values (HM_CHAIN_PRIO %d): %.1f us per launch; per wave (s_memtime ticks): sum-store %.0f, RS+A build %.0f, tiles %.0f, vmcnt wait %.0f\n",
+           nvals, wide ? kChainPrio<25> : kChainPrio<13>, ms * 1e3 / reps, z[0] / waves, z[1] / waves, z[2] / waves, z[3] / waves);
+    finish_table(hp, nvals);
 #else
     printf("chain %d values: %.1f us per launch\n", nvals, ms * 1e3 / reps);
 #endif
