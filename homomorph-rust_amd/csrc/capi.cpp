@@ -102,7 +102,9 @@ uint16_t min_d_over_delta(hm_op op) { // src/impls/numbers.rs:27-50
     case HM_OP_XOR: case HM_OP_NOT: return 1;
     case HM_OP_ADD: return 21;
     case HM_OP_MUL: case HM_OP_MUL_SIGNED: return 64;
-    default: break; // HM_OP_SUB .. HM_OP_GE depend on the width: borrow_min_d_over_delta
+    case HM_OP_SELECT: return 5; // 2m + 1 for c x_i of fresh bits, m = 2
+    default: break; // HM_OP_SUB .. HM_OP_GE, HM_OP_MIN, HM_OP_MAX depend on the width:
+                    // borrow_min_d_over_delta
     }
     return 0xFFFF;
 }
@@ -110,12 +112,15 @@ uint16_t min_d_over_delta(hm_op op) { // src/impls/numbers.rs:27-50
 bool is_borrow_op(hm_op op) { return op >= HM_OP_SUB && op <= HM_OP_GE; }
 bool is_compare_op(hm_op op) { return op >= HM_OP_EQ && op <= HM_OP_GE; }
 bool is_ordering_op(hm_op op) { return op >= HM_OP_LT && op <= HM_OP_GE; }
+bool is_minmax_op(hm_op op) { return op == HM_OP_MIN || op == HM_OP_MAX; }
+bool needs_width(hm_op op) { return is_borrow_op(op) || is_minmax_op(op); }
 
 // 2m + 1 with m the borrow circuit's degree in fresh input bits: nbits + 1 for the orderings
-// (the borrow out of the top bit), nbits for subtraction and equality.  A fresh bit's noise has
-// degree delta + 1 <= 2 delta, so d >= (2m + 1) delta gives m (delta + 1) < d.
+// (the borrow out of the top bit), nbits for subtraction and equality, nbits + 2 for min / max
+// (that borrow times x_i).  A fresh bit's noise has degree delta + 1 <= 2 delta, so
+// d >= (2m + 1) delta gives m (delta + 1) < d.
 uint16_t borrow_min_d_over_delta(hm_op op, uint32_t nbits) {
-    const uint32_t m = nbits + (is_ordering_op(op) ? 1u : 0u);
+    const uint32_t m = nbits + (is_ordering_op(op) ? 1u : is_minmax_op(op) ? 2u : 0u);
     return (uint16_t)(2 * m + 1);
 }
 
@@ -598,7 +603,7 @@ hm_status hm_ctx_set_mul_products(hm_ctx *c, uint32_t products) try {
 } HM_ABI_CATCH
 
 hm_status hm_validate_operation(const hm_ctx *c, hm_op op, uint16_t *req) try {
-    if (!c || is_borrow_op(op)) return HM_ERR_INVALID_ARGUMENT; // those need a width (_bits)
+    if (!c || needs_width(op)) return HM_ERR_INVALID_ARGUMENT; // those need a width (_bits)
     const uint16_t m = min_d_over_delta(op);
     if (req) *req = m;
     if ((uint32_t)c->d < (uint32_t)m * (uint32_t)c->delta) return HM_ERR_INVALID_PARAMETERS;
@@ -606,7 +611,7 @@ hm_status hm_validate_operation(const hm_ctx *c, hm_op op, uint16_t *req) try {
 } HM_ABI_CATCH
 
 hm_status hm_validate_operation_bits(const hm_ctx *c, hm_op op, uint32_t nbits, uint16_t *req) try {
-    if (!is_borrow_op(op)) return hm_validate_operation(c, op, req);
+    if (!needs_width(op)) return hm_validate_operation(c, op, req);
     if (!c || nbits == 0 || nbits > HM_MAX_BITS) return HM_ERR_INVALID_ARGUMENT;
     const uint16_t m = borrow_min_d_over_delta(op, nbits);
     if (req) *req = m;
@@ -677,6 +682,32 @@ hm_status hm_compare_out_bounds(hm_op cmp, uint32_t L, const uint32_t *a, const 
     out[0] = (uint32_t)r;
     for (int k = 1; k < 8; ++k) out[k] = 0;
     return HM_OK;
+} HM_ABI_CATCH
+
+// Degree bounds of select, min and max: the condition's bound (for min / max
+// the last borrow's, wb_nbits) plus the wider operand's, bit by bit.
+static hm_status choice_bounds(uint32_t L, int64_t cond, const uint32_t *a, const uint32_t *b,
+                               uint32_t *out) {
+    for (uint32_t i = 0; i < L; ++i) {
+        const int64_t s = cond + std::max(a[i], b[i]);
+        if (s >= (int64_t)1 << 30) return HM_ERR_UNSUPPORTED;
+        out[i] = (uint32_t)s;
+    }
+    return HM_OK;
+}
+
+hm_status hm_select_out_bounds(uint32_t L, uint32_t cond_bound0, const uint32_t *a,
+                               const uint32_t *b, uint32_t *out) try {
+    if (!a || !b || !out || L == 0 || L > HM_MAX_BITS) return HM_ERR_INVALID_ARGUMENT;
+    return choice_bounds(L, cond_bound0, a, b, out);
+} HM_ABI_CATCH
+
+hm_status hm_minmax_out_bounds(uint32_t L, const uint32_t *a, const uint32_t *b,
+                               uint32_t *out) try {
+    if (!a || !b || !out || L == 0 || L > HM_MAX_BITS) return HM_ERR_INVALID_ARGUMENT;
+    std::vector<int64_t> wb;
+    if (!borrow_bounds(L, a, b, wb)) return HM_ERR_UNSUPPORTED;
+    return choice_bounds(L, wb[L], a, b, out);
 } HM_ABI_CATCH
 
 } // extern "C"
@@ -1132,6 +1163,95 @@ hm_status hm_compare_batch(hm_ctx *c, hm_op cmp, const hm_batch *a, const hm_bat
     const bool ord = is_ordering_op(cmp);
     return borrow_run(c, ord ? kBorrowLt : kBorrowEq, flip, ord && is_signed != 0, a, b, out,
                       need[0]);
+} HM_ABI_CATCH
+
+// out's limbs or degree words share device memory with in's
+static bool overlaps(const hm_batch *out, const hm_batch *in) {
+    auto cross = [](const void *p, uint64_t pn, const void *q, uint64_t qn) {
+        const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+        return pn && qn && a < b + qn && b < a + pn;
+    };
+    return cross(out->limbs, 8 * out->n * hm_batch_stride(out->nbits, out->bound), in->limbs,
+                 8 * in->n * hm_batch_stride(in->nbits, in->bound)) ||
+           cross(out->degree, 4 * out->n * out->nbits, in->degree, 4 * in->n * in->nbits);
+}
+
+hm_status hm_minmax_batch(hm_ctx *c, hm_op which, const hm_batch *a, const hm_batch *b,
+                          int is_signed, hm_batch *out) try {
+    if (!c || !a || !b || !out || !is_minmax_op(which)) return HM_ERR_INVALID_ARGUMENT;
+    if (hm_status st = check_batch(a); st) return st;
+    if (hm_status st = check_batch(b); st) return st;
+    if (hm_status st = check_batch(out); st) return st;
+    if (b->nbits != a->nbits || b->n != a->n || out->nbits != a->nbits || out->n != a->n)
+        return HM_ERR_INVALID_ARGUMENT;
+    const uint32_t L = a->nbits;
+    if (hm_status st = hm_validate_operation_bits(c, which, L, nullptr); st) return st;
+    std::vector<uint32_t> need(L);
+    if (hm_status st = hm_minmax_out_bounds(L, a->bound, b->bound, need.data()); st) return st;
+    if (!covers(out, need) || overlaps(out, a) || overlaps(out, b)) return HM_ERR_INVALID_ARGUMENT;
+    if (a->n == 0) return HM_OK;
+    std::vector<int64_t> wb;
+    borrow_bounds(L, a->bound, b->bound, wb);
+    uint32_t SA = 2, SB = 2;
+    for (uint32_t i = 0; i < L; ++i) {
+        SA = std::max(SA, 2 * cap_of(a->bound[i]));
+        SB = std::max(SB, 2 * cap_of(b->bound[i]));
+    }
+    const uint32_t SX = std::max(SA, SB);
+    MinMaxArgs G{};
+    G.is_max = which == HM_OP_MAX, G.sgn = is_signed != 0;
+    // borrow_run's layout with chain = wb_L: the phase-2 product x_i w_L spans
+    // words(x_i) + words(w_L) <= SX + wb_L / 32 + 1 words, like the widest p_i w_i
+    G.oA = 0, G.oB = SA + 2, G.oX = G.oB + SB + 2, G.oP = G.oX + SX + 2, G.oG = G.oP + SX + 2;
+    G.oW = G.oG + SA + SB + 2;
+    G.cw = SX + (uint32_t)(wb[L] / 32) + 3;
+    G.lds_per_wave = G.oW + 2 * G.cw;
+    if ((size_t)G.lds_per_wave * 16 > 160 * 1024) return HM_ERR_UNSUPPORTED;
+    G.a = batch_arg(a), G.b = batch_arg(b), G.out = batch_arg(out);
+    G.n = a->n, G.nbits = L;
+    G.status = c->d_status;
+    fill_bounds(G.ab, a);
+    fill_bounds(G.bb, b);
+    fill_bounds(G.ob, out);
+    DeviceGuard g(c->device);
+    return launch_minmax(G, c->stream) ? hip_fail(c, hipGetLastError()) : HM_OK;
+} HM_ABI_CATCH
+
+hm_status hm_select_batch(hm_ctx *c, const hm_batch *cond, const hm_batch *a, const hm_batch *b,
+                          hm_batch *out) try {
+    if (!c || !cond || !a || !b || !out) return HM_ERR_INVALID_ARGUMENT;
+    for (const hm_batch *x : {cond, a, b, (const hm_batch *)out})
+        if (hm_status st = check_batch(x); st) return st;
+    if (cond->nbits != 8 || cond->n != a->n || b->nbits != a->nbits || b->n != a->n ||
+        out->nbits != a->nbits || out->n != a->n)
+        return HM_ERR_INVALID_ARGUMENT;
+    if (hm_status st = hm_validate_operation(c, HM_OP_SELECT, nullptr); st) return st;
+    const uint32_t L = a->nbits;
+    std::vector<uint32_t> need(L);
+    if (hm_status st = hm_select_out_bounds(L, cond->bound[0], a->bound, b->bound, need.data()); st)
+        return st;
+    if (!covers(out, need) || overlaps(out, cond) || overlaps(out, a) || overlaps(out, b))
+        return HM_ERR_INVALID_ARGUMENT;
+    if (a->n == 0) return HM_OK;
+    uint32_t SA = 2, SB = 2;
+    for (uint32_t i = 0; i < L; ++i) {
+        SA = std::max(SA, 2 * cap_of(a->bound[i]));
+        SB = std::max(SB, 2 * cap_of(b->bound[i]));
+    }
+    const uint32_t SX = std::max(SA, SB), SC = 2 * cap_of(cond->bound[0]);
+    SelectArgs G{};
+    // c | a_i | b_i | x_i | the product c x_i + b_i: words(c) + words(x_i) <= SC + SX words
+    G.oC = 0, G.oA = SC + 2, G.oB = G.oA + SA + 2, G.oX = G.oB + SB + 2, G.oT = G.oX + SX + 2;
+    G.lds_per_wave = G.oT + SC + SX + 2;
+    if ((size_t)G.lds_per_wave * 16 > 160 * 1024) return HM_ERR_UNSUPPORTED;
+    G.cond = batch_arg(cond), G.a = batch_arg(a), G.b = batch_arg(b), G.out = batch_arg(out);
+    G.n = a->n, G.nbits = L, G.cbound = cond->bound[0];
+    G.status = c->d_status;
+    fill_bounds(G.ab, a);
+    fill_bounds(G.bb, b);
+    fill_bounds(G.ob, out);
+    DeviceGuard g(c->device);
+    return launch_select(G, c->stream) ? hip_fail(c, hipGetLastError()) : HM_OK;
 } HM_ABI_CATCH
 
 // ------------------------------------------------------------------ polynomial primitives

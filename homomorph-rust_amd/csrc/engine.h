@@ -136,6 +136,36 @@ struct BorrowArgs {
     Bounds ab, bb, ob;
 };
 
+// min / max on the same chain (kernels.hip minmax_kernel), one wavefront per
+// value in the LDS layout of BorrowArgs.  Phase 1 is the kBorrowLt chain: it leaves w_nbits (the
+// polynomial a < b returns) in one borrow buffer.  Phase 2 walks the bits again:
+//   min  out_i = b_i + w_nbits x_i      max  out_i = a_i + w_nbits x_i      (x = a + b)
+// each product formed into the other borrow buffer and stored from there.
+struct MinMaxArgs {
+    uint32_t is_max;   // phase 2 adds a_i (max) instead of b_i (min)
+    uint32_t sgn;      // signed type: bit nbits - 1 generates a_i b_i + a_i
+    BatchArg a, b, out;
+    uint64_t n;
+    uint32_t nbits;
+    uint32_t lds_per_wave, oA, oB, oX, oP, oG, oW; // as BorrowArgs
+    uint32_t cw;       // words of each borrow buffer: the widest of p_i w_i and x_i w_nbits
+    int *status;
+    Bounds ab, bb, ob;
+};
+
+// Oblivious choice (kernels.hip select_kernel): out_i = b_i + c x_i with c bit 0
+// of a Ciphered<bool> (its bits 1..7 are not read), one wavefront per value.  c is loaded once per
+// value; per bit a_i, b_i and x_i are formed in LDS and one product goes to the buffer at oT.
+struct SelectArgs {
+    BatchArg cond, a, b, out;
+    uint64_t n;
+    uint32_t nbits;    // bits of a, b and out (cond has 8)
+    uint32_t cbound;   // degree bound of cond's bit 0
+    uint32_t lds_per_wave, oC, oA, oB, oX, oT; // word offsets in a wave's LDS slice
+    int *status;
+    Bounds ab, bb, ob;
+};
+
 // Column-parallel carry-save multiplier (mul_engine.hip, mul_host.cpp).  Column i of
 // mul_unsigned_internal (common.rs:66-105) XORs its items x_0..x_{n-1} (the partial products
 // a_j b_{i-j}, then the previous column's carries) into result_i and pushes the carry
@@ -416,6 +446,8 @@ int launch_encrypt(const EncArgs &a, void *stream);
 int launch_decrypt(const DecArgs &a, void *stream);
 int launch_gate(const GateArgs &a, void *stream);
 int launch_borrow(const BorrowArgs &a, void *stream);
+int launch_minmax(const MinMaxArgs &a, void *stream);
+int launch_select(const SelectArgs &a, void *stream);
 int launch_mul_stage(const MulStageArgs &a, void *stream);
 int launch_mul_pp(const MulPPArgs &a, void *stream);
 int launch_mul_scan(const MulScanArgs &a, void *stream);

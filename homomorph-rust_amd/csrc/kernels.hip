@@ -2,7 +2,9 @@
 //   gate_kernel     elementwise AND/OR/XOR/NOT (common.rs:5-35)
 //   borrow_kernel   subtraction, ==, !=, <, <=, >, >= as one ripple-borrow chain (no reference
 //                   circuit: DESIGN.md s4.4a)
-//   poly_* kernels  single-polynomial primitives for unit parity (polynomial.rs:190-365)
+//   minmax_kernel   min / max: that chain's last borrow times a_i + b_i, in one launch (s4.4b)
+//   select_kernel   cond ? a : b on an encrypted bool (s4.4b)
+//   poly_* kernels single-polynomial primitives for unit parity (polynomial.rs:190-365)
 // (adder: adder.hip; cipher: cipher.hip; carry-save multiplier: mul_engine.hip)
 #include <hip/hip_runtime.h>
 
@@ -154,6 +156,114 @@ int launch_borrow(const BorrowArgs &g, void *stream) {
     const uint64_t blocks = (g.n + wpb - 1) / wpb;
     if (blocks == 0) return 0;
     hipLaunchKernelGGL(borrow_kernel, dim3((unsigned)blocks), dim3(64 * wpb),
+                       (size_t)g.lds_per_wave * 4 * wpb, (hipStream_t)stream, g);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ---------------------------------------------------------------------------------------------
+// min / max (MinMaxArgs): the kBorrowLt chain above, then out_i = b_i + w_n x_i
+// (min) or a_i + w_n x_i (max) with w_n kept in LDS.  The chain step is written again here so that
+// borrow_kernel's code stays as it is.
+__global__ void __launch_bounds__(256) minmax_kernel(MinMaxArgs G) {
+    extern __shared__ uint32_t lds[];
+    const int wave = (int)rfl(threadIdx.x >> 6); // wave-uniform by construction
+    const uint64_t e = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave;
+    if (e >= G.n) return;
+    uint32_t *L = lds + (size_t)wave * G.lds_per_wave;
+    uint32_t *Ab = L + G.oA, *Bb = L + G.oB, *X = L + G.oX, *P = L + G.oP, *Gt = L + G.oG;
+    uint32_t *W = L + G.oW, *Wn = W + G.cw;
+    const uint64_t *pa = G.a.limbs + e * G.a.stride;
+    const uint64_t *pb = G.b.limbs + e * G.b.stride;
+    uint64_t *po = G.out.limbs + e * G.out.stride;
+    uint32_t offa = 0, offb = 0, offo = 0;
+    int nw = 0, nout; // w_0 = 0
+    // phase 1: w_{i+1} = a_i b_i + b_i + p_i w_i through the top bit
+    for (uint32_t i = 0; i < G.nbits; ++i) {
+        const int na = load_bit(pa + offa, rfl(G.a.degree[e * G.nbits + i]), G.ab.b[i], Ab, G.status);
+        const int nb = load_bit(pb + offb, rfl(G.b.degree[e * G.nbits + i]), G.bb.b[i], Bb, G.status);
+        wsync();
+        int nx, np;
+        xor_and_not(Ab, na, Bb, nb, X, P, &nx, &np);
+        wsync();
+        const bool top = G.sgn && i + 1 == G.nbits; // the signed top bit generates a_i b_i + a_i
+        const int ng = words_of(wave_mul<kQSmall, 8>(Ab, na, Bb, nb, top ? Ab : Bb, top ? na : nb,
+                                                     Gt, &nout));
+        wsync();
+        nw = words_of(wave_mul<kQSmall, 8>(P, np, W, nw, Gt, ng, Wn, &nout));
+        wsync();
+        uint32_t *t = W;
+        W = Wn, Wn = t;
+        offa += cap_of(G.ab.b[i]);
+        offb += cap_of(G.bb.b[i]);
+    }
+    // phase 2: W holds w_n; every product goes to Wn and is stored from there
+    offa = 0, offb = 0;
+    for (uint32_t i = 0; i < G.nbits; ++i) {
+        const int na = load_bit(pa + offa, rfl(G.a.degree[e * G.nbits + i]), G.ab.b[i], Ab, G.status);
+        const int nb = load_bit(pb + offb, rfl(G.b.degree[e * G.nbits + i]), G.bb.b[i], Bb, G.status);
+        wsync();
+        const int nx = words_of(wave_xor(Ab, na, Bb, nb, X));
+        wsync();
+        const int nt = words_of(wave_mul<kQSmall, 8>(X, nx, W, nw, G.is_max ? Ab : Bb,
+                                                     G.is_max ? na : nb, Wn, &nout));
+        wsync();
+        store_xor_bit(Wn, nt, nullptr, 0, po + offo, G.ob.b[i], G.out.degree + e * G.nbits + i,
+                      G.status);
+        wsync();
+        offa += cap_of(G.ab.b[i]);
+        offb += cap_of(G.bb.b[i]);
+        offo += cap_of(G.ob.b[i]);
+    }
+}
+
+int launch_minmax(const MinMaxArgs &g, void *stream) {
+    const int wpb = 4;
+    const uint64_t blocks = (g.n + wpb - 1) / wpb;
+    if (blocks == 0) return 0;
+    hipLaunchKernelGGL(minmax_kernel, dim3((unsigned)blocks), dim3(64 * wpb),
+                       (size_t)g.lds_per_wave * 4 * wpb, (hipStream_t)stream, g);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// Oblivious choice (SelectArgs): out_i = b_i + c x_i, c loaded once per value.
+// x_i is the uniform operand of the product (it is short when c comes out of a comparison).
+__global__ void __launch_bounds__(256) select_kernel(SelectArgs G) {
+    extern __shared__ uint32_t lds[];
+    const int wave = (int)rfl(threadIdx.x >> 6); // wave-uniform by construction
+    const uint64_t e = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave;
+    if (e >= G.n) return;
+    uint32_t *L = lds + (size_t)wave * G.lds_per_wave;
+    uint32_t *C = L + G.oC, *Ab = L + G.oA, *Bb = L + G.oB, *X = L + G.oX, *T = L + G.oT;
+    const uint64_t *pa = G.a.limbs + e * G.a.stride;
+    const uint64_t *pb = G.b.limbs + e * G.b.stride;
+    uint64_t *po = G.out.limbs + e * G.out.stride;
+    // bit 0 of the Ciphered<bool> is the first polynomial of the value
+    const int nc = load_bit(G.cond.limbs + e * G.cond.stride, rfl(G.cond.degree[e * 8]), G.cbound,
+                            C, G.status);
+    uint32_t offa = 0, offb = 0, offo = 0;
+    for (uint32_t i = 0; i < G.nbits; ++i) {
+        const int na = load_bit(pa + offa, rfl(G.a.degree[e * G.nbits + i]), G.ab.b[i], Ab, G.status);
+        const int nb = load_bit(pb + offb, rfl(G.b.degree[e * G.nbits + i]), G.bb.b[i], Bb, G.status);
+        wsync();
+        const int nx = words_of(wave_xor(Ab, na, Bb, nb, X));
+        wsync();
+        int nout;
+        const int nt = words_of(wave_mul<kQSmall, 8>(X, nx, C, nc, Bb, nb, T, &nout));
+        wsync();
+        store_xor_bit(T, nt, nullptr, 0, po + offo, G.ob.b[i], G.out.degree + e * G.nbits + i,
+                      G.status);
+        wsync();
+        offa += cap_of(G.ab.b[i]);
+        offb += cap_of(G.bb.b[i]);
+        offo += cap_of(G.ob.b[i]);
+    }
+}
+
+int launch_select(const SelectArgs &g, void *stream) {
+    const int wpb = 4;
+    const uint64_t blocks = (g.n + wpb - 1) / wpb;
+    if (blocks == 0) return 0;
+    hipLaunchKernelGGL(select_kernel, dim3((unsigned)blocks), dim3(64 * wpb),
                        (size_t)g.lds_per_wave * 4 * wpb, (hipStream_t)stream, g);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -31,10 +31,12 @@ __all__ = [
     "HomomorphicAddition", "HomomorphicMultiplication",
     "HomomorphicSubtraction", "HomomorphicEqual", "HomomorphicNotEqual", "HomomorphicLessThan",
     "HomomorphicLessEqual", "HomomorphicGreaterThan", "HomomorphicGreaterEqual",
+    "HomomorphicSelect", "HomomorphicMin", "HomomorphicMax",
     "OperationError", "ContextCryptoError", "CipherError", "EngineError", "LibraryMissing",
     "EngineGraph",
     "add_out_bounds", "mul_out_bounds", "gate_out_bounds", "sub_out_bounds",
-    "compare_out_bounds", "batch_stride", "caps",
+    "compare_out_bounds", "select_out_bounds", "minmax_out_bounds", "batch_stride", "caps",
+    "select_into", "minmax_into",
 ]
 
 
@@ -152,6 +154,29 @@ class HomomorphicGreaterThan(_Compare):
 
 class HomomorphicGreaterEqual(_Compare):
     CODE, EXTRA_DEGREE = _lib.OP_GE, 1
+
+
+class HomomorphicMin(_BorrowOp):
+    """min(a, b): b_i + w (a_i + b_i) with w the polynomial a < b returns."""
+    CODE, EXTRA_DEGREE = _lib.OP_MIN, 2
+
+
+class HomomorphicMax(_BorrowOp):
+    """max(a, b): a_i + w (a_i + b_i) on the same chain."""
+    CODE, EXTRA_DEGREE = _lib.OP_MAX, 2
+
+
+class HomomorphicSelect(_Op):
+    """cond ? a : b, obliviously: ctx.apply_n(HomomorphicSelect, [cond, a, b]) or
+    ctx.select(cond, a, b).  The requirement covers fresh operands, the condition included, as
+    the reference's gate requirements do; for a condition that came out of a comparison of n-bit
+    values check HomomorphicMin's: ctx.validate_operation(HomomorphicMin, n)."""
+    MIN_D_OVER_DELTA, CODE = 5, _lib.OP_SELECT
+
+    @classmethod
+    def apply(cls, ctx: "Context", args) -> "Ciphered":
+        cond, a, b = args
+        return ctx.select(cond, a, b)
 
 
 def _is_borrow(op) -> bool:
@@ -279,6 +304,25 @@ def compare_out_bounds(op, a_bound, b_bound) -> np.ndarray:
     out = np.zeros(8, dtype=np.uint32)
     _check(lib().hm_compare_out_bounds(op.CODE, a.size, _p32(a), _p32(b), _p32(out)),
            "hm_compare_out_bounds")
+    return out
+
+
+def select_out_bounds(cond_bound0, a_bound, b_bound) -> np.ndarray:
+    """hm_select_out_bounds: per-bit bounds of select(cond, a, b) for a condition whose bit 0
+    has the bound cond_bound0."""
+    a, b = _u32(a_bound), _u32(b_bound)
+    out = np.zeros_like(a)
+    _check(lib().hm_select_out_bounds(a.size, int(cond_bound0), _p32(a), _p32(b), _p32(out)),
+           "hm_select_out_bounds")
+    return out
+
+
+def minmax_out_bounds(a_bound, b_bound) -> np.ndarray:
+    """hm_minmax_out_bounds: per-bit bounds of min(a, b) and of max(a, b)."""
+    a, b = _u32(a_bound), _u32(b_bound)
+    out = np.zeros_like(a)
+    _check(lib().hm_minmax_out_bounds(a.size, _p32(a), _p32(b), _p32(out)),
+           "hm_minmax_out_bounds")
     return out
 
 
@@ -759,11 +803,26 @@ class Context:
             out = Ciphered.empty(a.n, need if out_bound is None else out_bound, self.device,
                                  np.dtype(np.bool_))
             compare_into(self, op, a, b, out, signed)
+        elif op in (HomomorphicMin, HomomorphicMax):
+            need = minmax_out_bounds(a.bound, b.bound)
+            out = Ciphered.empty(a.n, need if out_bound is None else out_bound, self.device,
+                                 a.plain_dtype)
+            minmax_into(self, op, a, b, out, signed)
         else:
             need = sub_out_bounds(a.bound, b.bound)
             out = Ciphered.empty(a.n, need if out_bound is None else out_bound, self.device,
                                  a.plain_dtype)
             sub_into(self, a, b, out)
+        return out
+
+    def select(self, cond: Ciphered, a: Ciphered, b: Ciphered, out_bound=None) -> Ciphered:
+        """cond ? a : b per value (hm_select_batch): cond is a batch of Ciphered<bool>, e.g. a
+        comparison's result or encrypted bools; the output keeps a's plaintext dtype."""
+        self.validate_operation(HomomorphicSelect)
+        need = select_out_bounds(cond.bound[0], a.bound, b.bound)
+        out = Ciphered.empty(a.n, need if out_bound is None else out_bound, self.device,
+                             a.plain_dtype)
+        select_into(self, cond, a, b, out)
         return out
 
     def mul_plan_work(self, a_bound, b_bound, k=None, signed=False) -> float:
@@ -887,6 +946,25 @@ def compare_into(ctx: Context, op, a: Ciphered, b: Ciphered, out: Ciphered, sign
     ctx._launch(lambda: lib().hm_compare_batch(ctx._h, op.CODE, ctypes.byref(ca), ctypes.byref(cb),
                                                int(bool(signed)), ctypes.byref(co)),
                 "hm_compare_batch")
+
+
+def select_into(ctx: Context, cond: Ciphered, a: Ciphered, b: Ciphered, out: Ciphered) -> None:
+    """hm_select_batch into a preallocated output (bounds: select_out_bounds)."""
+    cc, ca, cb, co = cond._c(), a._c(), b._c(), out._c()
+    ctx._launch(lambda: lib().hm_select_batch(ctx._h, ctypes.byref(cc), ctypes.byref(ca),
+                                              ctypes.byref(cb), ctypes.byref(co)),
+                "hm_select_batch")
+
+
+def minmax_into(ctx: Context, op, a: Ciphered, b: Ciphered, out: Ciphered, signed=None) -> None:
+    """hm_minmax_batch (op: HomomorphicMin or HomomorphicMax) into a preallocated output
+    (bounds: minmax_out_bounds).  signed defaults from a's plaintext dtype, as for comparisons."""
+    if signed is None:
+        signed = a.plain_dtype is not None and np.issubdtype(a.plain_dtype, np.signedinteger)
+    ca, cb, co = a._c(), b._c(), out._c()
+    ctx._launch(lambda: lib().hm_minmax_batch(ctx._h, op.CODE, ctypes.byref(ca), ctypes.byref(cb),
+                                              int(bool(signed)), ctypes.byref(co)),
+                "hm_minmax_batch")
 
 
 def mul_low_into(ctx: Context, a: Ciphered, b: Ciphered, k: int, out: Ciphered) -> None:

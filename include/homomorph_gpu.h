@@ -34,10 +34,12 @@
 extern "C" {
 #endif
 
-#define HM_ABI_VERSION 6 /* 4: kernel timing by device stamps (HM_TIME_*), hm_ctx_last_hip_error;
+#define HM_ABI_VERSION 7 /* 4: kernel timing by device stamps (HM_TIME_*), hm_ctx_last_hip_error;
                             5: hm_ctx_clear_kernel_timing, hm_ctx_set_mul_scratch;
                             6: HM_OP_SUB .. HM_OP_GE, hm_sub_batch, hm_compare_batch, their bounds,
-                               hm_validate_operation_bits */
+                               hm_validate_operation_bits;
+                            7: HM_OP_SELECT, HM_OP_MIN, HM_OP_MAX, hm_select_batch,
+                               hm_minmax_batch, their bounds */
 #define HM_MAX_BITS 128 /* u128 is the widest type with impls (src/impls/numbers/uint.rs:58) */
 
 typedef enum hm_status {
@@ -90,6 +92,17 @@ typedef enum hm_op {
     HM_OP_LE = 11,            /* HomomorphicLessEqual        a <= b */
     HM_OP_GT = 12,            /* HomomorphicGreaterThan      a >  b */
     HM_OP_GE = 13,            /* HomomorphicGreaterEqual     a >= b */
+    /* Consumers of a comparison's Ciphered<bool>, on the same rule 2m + 1.
+     * SELECT: out_i = b_i + c (a_i + b_i), m = 2, min d/delta 5 at any width.  As the reference's
+     * gate requirements do, that number covers FRESH operands, the condition included.  A
+     * condition that came out of a comparison carries that comparison's depth: for c = (a < b)
+     * on fresh n-bit values the whole circuit is HM_OP_MIN's, and the caller checks that
+     * requirement (hm_validate_operation_bits(HM_OP_MIN, n)).
+     * MIN / MAX: the borrow out of the top bit times a_i + b_i, m = n + 2, min d/delta 2n + 5
+     * (u8 21, u16 37, u32 69, u64 133): width dependent, like HM_OP_SUB .. HM_OP_GE. */
+    HM_OP_SELECT = 14,        /* HomomorphicSelect           cond ? a : b,  min d/delta 5 */
+    HM_OP_MIN = 15,           /* HomomorphicMin              min(a, b) */
+    HM_OP_MAX = 16,           /* HomomorphicMax              max(a, b) */
 } hm_op;
 
 typedef struct hm_ctx hm_ctx;
@@ -242,8 +255,9 @@ hm_status hm_validate_operation(const hm_ctx *ctx, hm_op op, uint16_t *required_
  * hm_validate_operation (nbits is not looked at).  HM_OP_SUB .. HM_OP_GE: the requirement
  * 2m + 1 above (u32: 65 for SUB / EQ / NE, 67 for the orderings), which gives m (delta + 1) < d,
  * so results on fresh inputs decrypt exactly; nbits outside 1..HM_MAX_BITS is
- * HM_ERR_INVALID_ARGUMENT.  hm_validate_operation itself has no width: it returns
- * HM_ERR_INVALID_ARGUMENT for HM_OP_SUB .. HM_OP_GE. */
+ * HM_ERR_INVALID_ARGUMENT.  HM_OP_MIN / HM_OP_MAX likewise: 2 nbits + 5 (u32: 69).
+ * HM_OP_SELECT has no width: both entries return 5.  hm_validate_operation itself has no width:
+ * it returns HM_ERR_INVALID_ARGUMENT for HM_OP_SUB .. HM_OP_GE, HM_OP_MIN and HM_OP_MAX. */
 hm_status hm_validate_operation_bits(const hm_ctx *ctx, hm_op op, uint32_t nbits,
                                      uint16_t *required_min_d_over_delta);
 
@@ -293,6 +307,16 @@ hm_status hm_sub_out_bounds(uint32_t nbits, const uint32_t *a_bound, const uint3
  * EQ / NE; out_bound[1..7] = 0 (null polynomials). */
 hm_status hm_compare_out_bounds(hm_op cmp, uint32_t nbits, const uint32_t *a_bound,
                                 const uint32_t *b_bound, uint32_t out_bound[8]);
+/* Output bounds of select(cond, a, b): out_bound[i] = cond_bound0 + max(a_i, b_i), with
+ * cond_bound0 the bound of the condition's bit 0 (its bits 1..7 are not read). */
+hm_status hm_select_out_bounds(uint32_t nbits, uint32_t cond_bound0, const uint32_t *a_bound,
+                               const uint32_t *b_bound, uint32_t *out_bound);
+/* Output bounds of min(a, b) and of max(a, b): out_bound[i] = wb_nbits + max(a_i, b_i) with the
+ * borrow recurrence of hm_sub_out_bounds.  (u32 at d + dp = 256: every bit 8704, 4384 limbs per
+ * value.)  Both entries: nbits outside 1..HM_MAX_BITS is HM_ERR_INVALID_ARGUMENT, a bound
+ * beyond the engine's degree range HM_ERR_UNSUPPORTED. */
+hm_status hm_minmax_out_bounds(uint32_t nbits, const uint32_t *a_bound, const uint32_t *b_bound,
+                               uint32_t *out_bound);
 /* stride (limbs per value) of a batch with these bounds */
 uint64_t hm_batch_stride(uint32_t nbits, const uint32_t *bound);
 
@@ -352,6 +376,24 @@ hm_status hm_sub_batch(hm_ctx *ctx, const hm_batch *a, const hm_batch *b, hm_bat
  * Validates cmp at a->nbits; otherwise as hm_sub_batch. */
 hm_status hm_compare_batch(hm_ctx *ctx, hm_op cmp, const hm_batch *a, const hm_batch *b,
                            int is_signed, hm_batch *out);
+/* cond ? a : b per value, obliviously: out_i = b_i + c (a_i + b_i) with c bit 0 of cond, a
+ * Ciphered<bool> batch (cond->nbits == 8; bits 1..7 are not read), e.g. a comparison's result or
+ * an encrypted bool.  A null c gives b's bits unchanged, the unit polynomial a's.  a, b, out: same
+ * nbits and n, cond->n == a->n; out bounds from hm_select_out_bounds(cond->bound[0]); out may not
+ * overlap cond, a or b (HM_ERR_INVALID_ARGUMENT).  Validates HM_OP_SELECT (see there for a
+ * condition that is not fresh).  One launch, no workspace; HM_ERR_UNSUPPORTED when a value does
+ * not fit a wavefront's share of LDS. */
+hm_status hm_select_batch(hm_ctx *ctx, const hm_batch *cond, const hm_batch *a, const hm_batch *b,
+                          hm_batch *out);
+/* min(a, b) or max(a, b) per value, which = HM_OP_MIN or HM_OP_MAX (anything else is
+ * HM_ERR_INVALID_ARGUMENT): with w = the borrow out of the top bit of a - b (exactly the
+ * polynomial hm_compare_batch(HM_OP_LT) returns, is_signed as there), min is
+ * out_i = b_i + w (a_i + b_i) and max out_i = a_i + w (a_i + b_i) -- bit for bit
+ * hm_select_batch(a < b, a, b) and hm_select_batch(a < b, b, a), in one launch and without w ever
+ * leaving the chip.  out bounds from hm_minmax_out_bounds; validates which at a->nbits; otherwise
+ * as hm_select_batch. */
+hm_status hm_minmax_batch(hm_ctx *ctx, hm_op which, const hm_batch *a, const hm_batch *b,
+                          int is_signed, hm_batch *out);
 
 /* ---------------- polynomial primitives (src/polynomial.rs), for unit parity ---------------- */
 /* Polynomial::add (polynomial.rs:190-213) per pair: out = a ^ b, exact degree. */
