@@ -2,19 +2,22 @@
 //
 // Owns the per-device context (keys, derived decrypt table, workspace, stream), validates every
 // call the way the reference's safe wrappers do (Context::validate_operation, src/context.rs:
-// 310-323; Parameters::new asserts, :87-94), computes static degree bounds and per-wave LDS carve-
-// outs, and launches the kernels of kernels.hip.  Never throws across the ABI.
+// 310-323; Parameters::new asserts, :87-94), computes static degree bounds and the per-wave LDS
+// carve-outs of the wave-per-value circuits, and launches the kernels.  The adder's plan comes
+// from add_host.h (plan_add), the multiplier's from mul_host.cpp.  Never throws across the ABI.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <new>
 #include <vector>
 
 #include <sys/random.h>
 
+#include "add_host.h"
 #include "ctx.h"
 
 using namespace hm;
@@ -140,6 +143,75 @@ bool covers(const hm_batch *out, const std::vector<uint32_t> &need) {
     for (uint32_t i = 0; i < out->nbits; ++i)
         if (out->bound[i] < need[i]) return false;
     return true;
+}
+
+// The operand check of the batch entries: check_batch on each operand in the order given (a null
+// one is its HM_ERR_INVALID_ARGUMENT, a bound beyond 2^30 its HM_ERR_UNSUPPORTED), then each has
+// the width asked of it (0: the operation's width, the first such operand's) and as many values
+// as the first.  Which status a call with several faults returns depends on the order of the
+// operands, on whether the entry tests every pointer first, and on where validate_operation sits
+// relative to this check: each entry keeps its own.
+struct Operand {
+    const hm_batch *x;
+    uint32_t nbits;
+};
+hm_status check_operands(std::initializer_list<Operand> ops) {
+    for (const Operand &o : ops)
+        if (hm_status st = check_batch(o.x); st) return st;
+    uint32_t width = 0;
+    for (const Operand &o : ops)
+        if (!o.nbits && !width) width = o.x->nbits;
+    for (const Operand &o : ops)
+        if (o.x->nbits != (o.nbits ? o.nbits : width) || o.x->n != ops.begin()->x->n)
+            return HM_ERR_INVALID_ARGUMENT;
+    return HM_OK;
+}
+
+// LDS words of the operand rows of the wave-per-value circuits: two words per limb of the widest
+// bit of a, of b (null: a unary gate, two words) and of either
+struct Slots {
+    uint32_t SA = 2, SB = 2, SX = 2;
+};
+Slots operand_slots(const hm_batch *a, const hm_batch *b) {
+    Slots s;
+    for (uint32_t i = 0; i < a->nbits; ++i) {
+        s.SA = std::max(s.SA, 2 * cap_of(a->bound[i]));
+        if (b) s.SB = std::max(s.SB, 2 * cap_of(b->bound[i]));
+    }
+    s.SX = std::max(s.SA, s.SB);
+    return s;
+}
+
+// The ripple-borrow chain's slice, chain = the degree bound of the last borrow (or equality
+// prefix) formed: a_i | b_i | x_i | p_i | generate term a_i b_i + b_i | two borrow buffers: the
+// widest product p_i w_i spans words(p_i) + words(w_i) <= SX + chain / 32 + 1 words
+BorrowLayout borrow_layout(const Slots &s, int64_t chain) {
+    BorrowLayout y{};
+    y.oA = 0, y.oB = s.SA + 2, y.oX = y.oB + s.SB + 2, y.oP = y.oX + s.SX + 2, y.oG = y.oP + s.SX + 2;
+    y.oW = y.oG + s.SA + s.SB + 2;
+    y.cw = s.SX + (uint32_t)(chain / 32) + 3;
+    y.lds_per_wave = y.oW + 2 * y.cw;
+    return y;
+}
+
+// The operands, counts, bounds and status word of an argument block (b null: a unary gate)
+template <class Args>
+void fill_io(Args &G, hm_ctx *c, const hm_batch *a, const hm_batch *b, const hm_batch *out) {
+    G.a = batch_arg(a), G.out = batch_arg(out);
+    G.n = a->n, G.nbits = a->nbits;
+    G.status = c->d_status;
+    fill_bounds(G.ab, a), fill_bounds(G.ob, out);
+    if (b) G.b = batch_arg(b), fill_bounds(G.bb, b);
+}
+
+// Launches a wave-per-value circuit over checked batches: four waves' LDS slices within a CU
+template <class Args>
+hm_status run_circuit(hm_ctx *c, Args &G, uint32_t lds_per_wave, const hm_batch *a,
+                      const hm_batch *b, const hm_batch *out, int (*launch)(const Args &, void *)) {
+    if ((size_t)lds_per_wave * 16 > 160 * 1024) return HM_ERR_UNSUPPORTED;
+    fill_io(G, c, a, b, out);
+    DeviceGuard g(c->device);
+    return launch(G, c->stream) ? hip_fail(c, hipGetLastError()) : HM_OK;
 }
 
 // Uploads the public key rows, and (when it fits an LDS budget) the encryption nibble table:
@@ -710,10 +782,6 @@ hm_status hm_minmax_out_bounds(uint32_t L, const uint32_t *a, const uint32_t *b,
     return choice_bounds(L, wb[L], a, b, out);
 } HM_ABI_CATCH
 
-} // extern "C"
-
-extern "C" {
-
 hm_status hm_mul_out_bounds(uint32_t L, const uint32_t *a, const uint32_t *b, int is_signed,
                             uint32_t *out) try {
     if (!a || !b || !out || L == 0 || L > HM_MAX_BITS) return HM_ERR_INVALID_ARGUMENT;
@@ -856,153 +924,21 @@ hm_status hm_decrypt_batch(hm_ctx *c, const hm_batch *in, uint8_t *out) try {
 hm_status hm_add_batch(hm_ctx *c, const hm_batch *a, const hm_batch *b, hm_batch *out) try {
     if (!c || !a || !b || !out) return HM_ERR_INVALID_ARGUMENT;
     if (hm_status st = hm_validate_operation(c, HM_OP_ADD, nullptr); st) return st;
-    for (const hm_batch *x : {a, b, (const hm_batch *)out})
-        if (hm_status st = check_batch(x); st) return st;
-    if (a->nbits != b->nbits || a->nbits != out->nbits || a->n != b->n || a->n != out->n)
-        return HM_ERR_INVALID_ARGUMENT;
+    if (hm_status st = check_operands({{a, 0}, {b, 0}, {out, 0}}); st) return st;
     const uint32_t L = a->nbits;
     std::vector<uint32_t> need(L);
     if (hm_status st = hm_add_out_bounds(L, a->bound, b->bound, need.data()); st) return st;
     if (!covers(out, need)) return HM_ERR_INVALID_ARGUMENT;
     if (a->n == 0) return HM_OK;
-
-    // Workspace slots (words) and LDS plans, from the static bounds
-    uint32_t cntA = 0, cntB = 0, cntAB = 0, cntP = 0, cntX = 1, SC = 2, maxPw = 0;
-    int64_t maxb = 0; // the largest input bound
-    int64_t cb = -1;
-    for (uint32_t i = 0; i < L; ++i) {
-        const int64_t ba = a->bound[i], bb = b->bound[i];
-        cntA = std::max(cntA, 2 * cap_of(a->bound[i]));
-        cntB = std::max(cntB, 2 * cap_of(b->bound[i]));
-        cntX = std::max(cntX, words_of_bound(std::max(ba, bb)));
-        maxb = std::max(maxb, std::max(ba, bb));
-        if (i + 1 < L) {
-            const int64_t x = std::max(ba, bb), ab = ba + bb, p = x + ab;
-            cntAB = std::max(cntAB, words_of_bound(ab));
-            cntP = std::max(cntP, words_of_bound(p));
-            maxPw = std::max(maxPw, words_of_bound(p));
-            SC = std::max(SC, std::max(words_of_bound(p) + words_of_bound(cb), words_of_bound(ab)) + 2);
-            cb = (cb < 0) ? ab : std::max(ab, p + cb);
-        }
-    }
-    cntAB = std::max(cntAB, 1u), cntP = std::max(cntP, 1u);
-    auto even = [](uint32_t v) { return (v + 1) & ~1u; };
+    // workspace slots, the prep's shape and the chain's LDS plan, from the static bounds
     AddArgs A{};
-    A.cntA = cntA, A.cntB = cntB, A.cntAB = cntAB, A.cntP = cntP, A.cntX = cntX;
-    // prep: enough waves per value to keep the chip busy, and at least enough that one wave's
-    // product rows (bits x multiplier words) fit its 64 lanes in two passes (bits are dealt in
-    // contiguous ranges)
-    {
-        const uint64_t want = (16384 + a->n - 1) / a->n;
-        // (rows_fit: waves per value for one pass of a wave's rows; big batches take two passes
-        // per wave -- half the waves: configs[4]'s prep 7.8 -> 5.7 ms per 131,072 adds, the
-        // headline's 4 waves per value unchanged, since its `want` is 4 already)
-        auto waves = [&](uint32_t rows) { // rows: product rows per bit
-            const uint64_t rows_fit = (L + std::max<uint32_t>(1, 64 / rows) - 1) /
-                                      std::max<uint32_t>(1, 64 / rows);
-            // (never fewer than ceil(L / 64): a wave's range is at most 64 bits -- a u128 add with
-            // one row per bit at a big batch asked for 1)
-            return (uint32_t)std::max<uint64_t>(
-                (L + 63) / 64, std::min<uint64_t>({std::max(want, (rows_fit + 1) / 2), 8, (uint64_t)L}));
-        };
-        // the top word of every a_i, b_i, x_i holds at most bit 32 (cntX - 1) = maxb: the prep can
-        // add its multiples as shifted copies instead of product rows -- worth it when the shorter
-        // rows save waves per value or row passes per wave (waves x passes; the headline: 2 passes
-        // -> 1 at 4 waves; one wave and one pass per value only pays for the copy passes, +8 us
-        // per 65,536 u8 adds)
-        const bool t1ok = cntX >= 2 && maxb % 32 == 0;
-        // row passes per wave at w waves per value (rows per bit)
-        auto passes = [&](uint32_t w, uint32_t rows) { return (((L + w - 1) / w) * rows + 63) / 64; };
-        const uint32_t w0 = waves(cntX), w1 = t1ok ? waves(cntX - 1) : w0;
-        A.top1 = t1ok && (uint64_t)w1 * passes(w1, cntX - 1) < (uint64_t)w0 * passes(w0, cntX);
-        A.wpv = waves(cntX - A.top1);
-        // one wave per value already (short values, big batch): several whole values per wave
-        // instead when their rows fit one pass (L a power of two: configs[0]'s u8 add, 2 values
-        // of 8 bits x 4 rows with the top-word copies; its prep cost is per wave)
-        A.vpw = 1, A.lgL = 0;
-        if (A.wpv == 1 && (L & (L - 1)) == 0 && a->n >= 16384) {
-            const uint32_t rows = cntX - (t1ok ? 1u : 0u);
-            const uint32_t v = std::min<uint32_t>(8, 64 / std::max<uint32_t>(1, L * rows));
-            if (v >= 2) {
-                A.vpw = v, A.top1 = t1ok;
-                while ((1u << A.lgL) < L) ++A.lgL;
-            }
-        }
-        // both operands of one bound 64 (CAP - 1), as fresh ciphertexts of d + d' = 64 (CAP - 1)
-        // are: the uniform prep (adder.hip add_prep_uniform_kernel), whose slot sizes are
-        // compile-time and which always takes the top-word copies, whatever A.top1 says; CAP = 5
-        // is the instance built (the headline)
-        A.ucap = 0;
-        if (A.vpw == 1 && t1ok) {
-            const uint32_t ub = a->bound[0], cap = cap_of(ub);
-            bool uni = cap == 5 && ub == 64 * (cap - 1);
-            for (uint32_t i = 0; i < L && uni; ++i) uni = a->bound[i] == ub && b->bound[i] == ub;
-            if (uni && cntA == 2 * cap && cntB == 2 * cap && cntX == 2 * cap - 1 &&
-                cntAB == 4 * cap - 3 && cntP == 6 * cap - 5)
-                A.ucap = cap;
-        }
-        const uint32_t bpw = A.vpw > 1 ? A.vpw * L : (L + A.wpv - 1) / A.wpv;
-        // (+ 2 bpw: with dAB / dP, stage_ab's bound / offset tables; a wave's range is at most 64 bits)
-        if (bpw > 64) return HM_ERR_UNSUPPORTED;
-        A.prep_lds = even(bpw * (cntA + cntB + cntX + cntAB + cntP) + 6 * bpw);
-        if ((size_t)A.prep_lds * 4 * 4 > 160 * 1024) return HM_ERR_UNSUPPORTED;
-    }
-    // chain: a carry buffer holds a whole tile of the widest width instantiated (PAD mode);
-    // each buffer sits above a zero halo of kHalo words
-    const uint32_t need_w = (SC + 63) / 64;
-    const uint32_t wmax = need_w <= 4 ? 4 : need_w <= 8 ? 8 : need_w <= 12 ? 12 : need_w <= 16 ? 16 : 24;
-    // PAD needs one tile per product (need_w <= 24) and one uniform chunk (P within kQBig
-    // words) so that window reads stay inside [-kHalo, 64*wmax)
-    A.pad = need_w <= 24 && maxPw <= 25;
-    uint32_t cw = SC;
-    if (A.pad) cw = std::max(cw, 64 * wmax);
-    A.cw = even(cw);
-    // staged chain (PAD only): one in-place carry buffer, and everything the chain reads per bit
-    // (x_i, ab_i, P_i, degrees) in LDS, so the loop issues no global loads at all
-    const uint32_t staged_lds =
-        even(A.cw + kHalo + (L - 1) * (cntP + cntAB) + L * cntX + 2 * L);
-    A.staged = A.pad && (size_t)staged_lds * 4 * kAddWavesPerBlock <= 160 * 1024;
-    A.chain_lds = A.staged ? staged_lds : even(2 * (A.cw + kHalo) + (L - 1) * cntP);
-    A.max_prod_words = SC;
-    if ((size_t)A.chain_lds * 4 * kAddWavesPerBlock > 160 * 1024) return HM_ERR_UNSUPPORTED;
-    // MFMA chain (adder_mfma.hip): P_i within 2*kMfmaChunks-1 words, ab_i within 64 words (two
-    // tiles), a bit's workspace record (x, P, ab, two degrees) within one 64-lane LDS-DMA; carry
-    // bits for every tile plus the 64-word window overhang of the ring fill
-    {
-        const uint32_t tiles = (SC + 31) / 32;
-        const uint32_t mf_cw = 32 * tiles + 64;
-        // the smallest chunk count whose plan fits: P_i within 2 NC - 1 words, ab_i within 64
-        // words (two tiles), the bit's record within kRecWords, and x_i below 32 words (the
-        // kernel XORs x into sum words 0..31 only; words from 32 up are the carry's, stored by the
-        // tiles), for the last bit as for every other; LDS (dynamic + the static record stage)
-        // for one block
-        auto plan = [&](auto cfg) -> uint32_t {
-            using Cfg = decltype(cfg);
-            const uint32_t lds = Cfg::kHalo + mf_cw + Cfg::kRingWords + Cfg::kRsWords;
-            const bool fits = maxPw <= 2 * Cfg::kChunks - 1 && cntAB <= 64 && cntX <= 32 &&
-                              cntX + cntP + cntAB + 2 <= (uint32_t)Cfg::kRecWords &&
-                              (256 + (size_t)lds * kAddWavesPerBlock + Cfg::kStageWords) * 4 <=
-                                  160 * 1024;
-            return fits ? lds : 0u;
-        };
-        uint32_t nc = 0, lds = 0;
-        if ((lds = plan(MfmaCfg<7>{}))) nc = 7;
-        else if ((lds = plan(MfmaCfg<13>{}))) nc = 13;
-        else if ((lds = plan(MfmaCfg<25>{}))) nc = 25;
-        if (!c->fp4_mfma) nc = 0;
-        A.mfma = c->add_chain != HM_ADD_CHAIN_VALU ? nc : 0u;
-        if (c->add_chain == HM_ADD_CHAIN_MFMA && !nc) return HM_ERR_UNSUPPORTED;
-        if (A.mfma) A.mf_cw = mf_cw, A.chain_lds = lds;
-    }
-    A.ws_stride = ((uint64_t)L * (cntAB + cntP + 2 + cntX) + 63) & ~(uint64_t)63;
+    const AddShape shape{L, a->bound, b->bound, a->n, c->add_chain, c->fp4_mfma};
+    if (hm_status st = plan_add(shape, A); st) return st;
     const size_t bytes = (size_t)A.ws_stride * 4 * a->n;
     DeviceGuard g(c->device);
     HM_HIP(c, grow(c, c->d_ws_add, c->ws_add_bytes, bytes));
     A.ws = c->d_ws_add;
-    A.a = batch_arg(a), A.b = batch_arg(b), A.out = batch_arg(out);
-    A.n = a->n, A.nbits = L;
-    A.status = c->d_status;
-    fill_bounds(A.ab, a), fill_bounds(A.bb, b), fill_bounds(A.ob, out);
+    fill_io(A, c, a, b, out);
     A.kt = c->ktimer(HM_TIME_ADD_CHAIN);
     // Two-stage pipeline (not while timing the chain): the batch in two halves, the second
     // half's prep on the auxiliary stream right after the first half's, so it runs beside the
@@ -1033,10 +969,7 @@ hm_status hm_mul_batch(hm_ctx *c, const hm_batch *a, const hm_batch *b, int is_s
     if (!c || !a || !b || !out) return HM_ERR_INVALID_ARGUMENT;
     if (hm_status st = hm_validate_operation(c, is_signed ? HM_OP_MUL_SIGNED : HM_OP_MUL, nullptr); st)
         return st;
-    for (const hm_batch *x : {a, b, (const hm_batch *)out})
-        if (hm_status st = check_batch(x); st) return st;
-    if (a->nbits != b->nbits || a->nbits != out->nbits || a->n != b->n || a->n != out->n)
-        return HM_ERR_INVALID_ARGUMENT;
+    if (hm_status st = check_operands({{a, 0}, {b, 0}, {out, 0}}); st) return st;
     return mul_columns(c, a, b, a->nbits, is_signed != 0, out);
 } HM_ABI_CATCH
 
@@ -1044,11 +977,8 @@ hm_status hm_mul_low_batch(hm_ctx *c, const hm_batch *a, const hm_batch *b, uint
                            hm_batch *out) try {
     if (!c || !a || !b || !out) return HM_ERR_INVALID_ARGUMENT;
     if (hm_status st = hm_validate_operation(c, HM_OP_MUL, nullptr); st) return st;
-    for (const hm_batch *x : {a, b, (const hm_batch *)out})
-        if (hm_status st = check_batch(x); st) return st;
-    if (a->nbits != b->nbits || k == 0 || k > a->nbits || out->nbits != k || a->n != b->n ||
-        a->n != out->n)
-        return HM_ERR_INVALID_ARGUMENT;
+    if (hm_status st = check_operands({{a, 0}, {b, 0}, {out, k}}); st) return st;
+    if (k == 0 || k > a->nbits) return HM_ERR_INVALID_ARGUMENT; // (k = 0 asked out for a's width)
     return mul_columns(c, a, b, k, false, out);
 } HM_ABI_CATCH
 
@@ -1057,81 +987,39 @@ hm_status hm_gate_batch(hm_ctx *c, hm_op gate, const hm_batch *a, const hm_batch
     if (!c || !a || !out) return HM_ERR_INVALID_ARGUMENT;
     if (gate > HM_OP_NOT) return HM_ERR_INVALID_ARGUMENT;
     if (hm_status st = hm_validate_operation(c, gate, nullptr); st) return st;
-    if (hm_status st = check_batch(a); st) return st;
-    if (hm_status st = check_batch(out); st) return st;
-    if (gate != HM_OP_NOT) {
-        if (!b) return HM_ERR_INVALID_ARGUMENT;
-        if (hm_status st = check_batch(b); st) return st;
-        if (b->nbits != a->nbits || b->n != a->n) return HM_ERR_INVALID_ARGUMENT;
-    }
-    if (out->nbits != a->nbits || out->n != a->n) return HM_ERR_INVALID_ARGUMENT;
+    if (gate == HM_OP_NOT) b = nullptr; // (a unary gate's b is not looked at)
+    // (out before b: the order this entry checks them in)
+    if (hm_status st = gate == HM_OP_NOT ? check_operands({{a, 0}, {out, 0}})
+                                         : check_operands({{a, 0}, {out, 0}, {b, 0}});
+        st)
+        return st;
     const uint32_t L = a->nbits;
     std::vector<uint32_t> need(L);
-    if (hm_status st = hm_gate_out_bounds(gate, L, a->bound, gate == HM_OP_NOT ? nullptr : b->bound,
-                                          need.data());
-        st)
+    if (hm_status st = hm_gate_out_bounds(gate, L, a->bound, b ? b->bound : nullptr, need.data()); st)
         return st;
     if (!covers(out, need)) return HM_ERR_INVALID_ARGUMENT;
     if (a->n == 0) return HM_OK;
-    uint32_t SA = 0, SB = 2;
-    for (uint32_t i = 0; i < L; ++i) {
-        SA = std::max(SA, 2 * cap_of(a->bound[i]));
-        if (gate != HM_OP_NOT) SB = std::max(SB, 2 * cap_of(b->bound[i]));
-    }
+    const Slots s = operand_slots(a, b);
     GateArgs G{};
     G.op = gate;
-    G.oA = 0, G.oB = SA + 2, G.oT = G.oB + SB + 2;
-    G.lds_per_wave = G.oT + 2 * (SA + SB) + 8;
-    if ((size_t)G.lds_per_wave * 16 > 160 * 1024) return HM_ERR_UNSUPPORTED;
-    G.a = batch_arg(a);
-    if (gate != HM_OP_NOT) G.b = batch_arg(b);
-    G.out = batch_arg(out);
-    G.n = a->n, G.nbits = L;
-    G.status = c->d_status;
-    fill_bounds(G.ab, a);
-    if (gate != HM_OP_NOT) fill_bounds(G.bb, b);
-    fill_bounds(G.ob, out);
-    DeviceGuard g(c->device);
-    return launch_gate(G, c->stream) ? hip_fail(c, hipGetLastError()) : HM_OK;
+    G.oA = 0, G.oB = s.SA + 2, G.oT = G.oB + s.SB + 2;
+    G.lds_per_wave = G.oT + 2 * (s.SA + s.SB) + 8;
+    return run_circuit(c, G, G.lds_per_wave, a, b, out, launch_gate);
 } HM_ABI_CATCH
 
 // The ripple-borrow kernel over checked batches (a, b: L bits; out covers its bounds).  chain: the
 // degree bound of the last borrow (or equality prefix) the kernel forms.
 static hm_status borrow_run(hm_ctx *c, int mode, bool flip, bool sgn, const hm_batch *a,
                             const hm_batch *b, hm_batch *out, int64_t chain) {
-    const uint32_t L = a->nbits;
-    uint32_t SA = 2, SB = 2;
-    for (uint32_t i = 0; i < L; ++i) {
-        SA = std::max(SA, 2 * cap_of(a->bound[i]));
-        SB = std::max(SB, 2 * cap_of(b->bound[i]));
-    }
-    const uint32_t SX = std::max(SA, SB);
     BorrowArgs G{};
     G.mode = mode, G.flip = flip, G.sgn = sgn;
-    // a_i | b_i | x_i | p_i | generate term a_i b_i + b_i | two borrow buffers: the widest
-    // product p_i w_i spans words(p_i) + words(w_i) <= SX + chain / 32 + 1 words
-    G.oA = 0, G.oB = SA + 2, G.oX = G.oB + SB + 2, G.oP = G.oX + SX + 2, G.oG = G.oP + SX + 2;
-    G.oW = G.oG + SA + SB + 2;
-    G.cw = SX + (uint32_t)(chain / 32) + 3;
-    G.lds_per_wave = G.oW + 2 * G.cw;
-    if ((size_t)G.lds_per_wave * 16 > 160 * 1024) return HM_ERR_UNSUPPORTED;
-    G.a = batch_arg(a), G.b = batch_arg(b), G.out = batch_arg(out);
-    G.n = a->n, G.nbits = L;
-    G.status = c->d_status;
-    fill_bounds(G.ab, a);
-    fill_bounds(G.bb, b);
-    fill_bounds(G.ob, out);
-    DeviceGuard g(c->device);
-    return launch_borrow(G, c->stream) ? hip_fail(c, hipGetLastError()) : HM_OK;
+    G.lay = borrow_layout(operand_slots(a, b), chain);
+    return run_circuit(c, G, G.lay.lds_per_wave, a, b, out, launch_borrow);
 }
 
 hm_status hm_sub_batch(hm_ctx *c, const hm_batch *a, const hm_batch *b, hm_batch *out) try {
     if (!c || !a || !b || !out) return HM_ERR_INVALID_ARGUMENT;
-    if (hm_status st = check_batch(a); st) return st;
-    if (hm_status st = check_batch(b); st) return st;
-    if (hm_status st = check_batch(out); st) return st;
-    if (b->nbits != a->nbits || b->n != a->n || out->nbits != a->nbits || out->n != a->n)
-        return HM_ERR_INVALID_ARGUMENT;
+    if (hm_status st = check_operands({{a, 0}, {b, 0}, {out, 0}}); st) return st;
     const uint32_t L = a->nbits;
     if (hm_status st = hm_validate_operation_bits(c, HM_OP_SUB, L, nullptr); st) return st;
     std::vector<uint32_t> need(L);
@@ -1146,11 +1034,7 @@ hm_status hm_sub_batch(hm_ctx *c, const hm_batch *a, const hm_batch *b, hm_batch
 hm_status hm_compare_batch(hm_ctx *c, hm_op cmp, const hm_batch *a, const hm_batch *b,
                            int is_signed, hm_batch *out) try {
     if (!c || !a || !b || !out || !is_compare_op(cmp)) return HM_ERR_INVALID_ARGUMENT;
-    if (hm_status st = check_batch(a); st) return st;
-    if (hm_status st = check_batch(b); st) return st;
-    if (hm_status st = check_batch(out); st) return st;
-    if (b->nbits != a->nbits || b->n != a->n || out->nbits != 8 || out->n != a->n)
-        return HM_ERR_INVALID_ARGUMENT;
+    if (hm_status st = check_operands({{a, 0}, {b, 0}, {out, 8}}); st) return st;
     const uint32_t L = a->nbits;
     if (hm_status st = hm_validate_operation_bits(c, cmp, L, nullptr); st) return st;
     std::vector<uint32_t> need(8);
@@ -1179,11 +1063,7 @@ static bool overlaps(const hm_batch *out, const hm_batch *in) {
 hm_status hm_minmax_batch(hm_ctx *c, hm_op which, const hm_batch *a, const hm_batch *b,
                           int is_signed, hm_batch *out) try {
     if (!c || !a || !b || !out || !is_minmax_op(which)) return HM_ERR_INVALID_ARGUMENT;
-    if (hm_status st = check_batch(a); st) return st;
-    if (hm_status st = check_batch(b); st) return st;
-    if (hm_status st = check_batch(out); st) return st;
-    if (b->nbits != a->nbits || b->n != a->n || out->nbits != a->nbits || out->n != a->n)
-        return HM_ERR_INVALID_ARGUMENT;
+    if (hm_status st = check_operands({{a, 0}, {b, 0}, {out, 0}}); st) return st;
     const uint32_t L = a->nbits;
     if (hm_status st = hm_validate_operation_bits(c, which, L, nullptr); st) return st;
     std::vector<uint32_t> need(L);
@@ -1192,39 +1072,18 @@ hm_status hm_minmax_batch(hm_ctx *c, hm_op which, const hm_batch *a, const hm_ba
     if (a->n == 0) return HM_OK;
     std::vector<int64_t> wb;
     borrow_bounds(L, a->bound, b->bound, wb);
-    uint32_t SA = 2, SB = 2;
-    for (uint32_t i = 0; i < L; ++i) {
-        SA = std::max(SA, 2 * cap_of(a->bound[i]));
-        SB = std::max(SB, 2 * cap_of(b->bound[i]));
-    }
-    const uint32_t SX = std::max(SA, SB);
     MinMaxArgs G{};
     G.is_max = which == HM_OP_MAX, G.sgn = is_signed != 0;
     // borrow_run's layout with chain = wb_L: the phase-2 product x_i w_L spans
     // words(x_i) + words(w_L) <= SX + wb_L / 32 + 1 words, like the widest p_i w_i
-    G.oA = 0, G.oB = SA + 2, G.oX = G.oB + SB + 2, G.oP = G.oX + SX + 2, G.oG = G.oP + SX + 2;
-    G.oW = G.oG + SA + SB + 2;
-    G.cw = SX + (uint32_t)(wb[L] / 32) + 3;
-    G.lds_per_wave = G.oW + 2 * G.cw;
-    if ((size_t)G.lds_per_wave * 16 > 160 * 1024) return HM_ERR_UNSUPPORTED;
-    G.a = batch_arg(a), G.b = batch_arg(b), G.out = batch_arg(out);
-    G.n = a->n, G.nbits = L;
-    G.status = c->d_status;
-    fill_bounds(G.ab, a);
-    fill_bounds(G.bb, b);
-    fill_bounds(G.ob, out);
-    DeviceGuard g(c->device);
-    return launch_minmax(G, c->stream) ? hip_fail(c, hipGetLastError()) : HM_OK;
+    G.lay = borrow_layout(operand_slots(a, b), wb[L]);
+    return run_circuit(c, G, G.lay.lds_per_wave, a, b, out, launch_minmax);
 } HM_ABI_CATCH
 
 hm_status hm_select_batch(hm_ctx *c, const hm_batch *cond, const hm_batch *a, const hm_batch *b,
                           hm_batch *out) try {
     if (!c || !cond || !a || !b || !out) return HM_ERR_INVALID_ARGUMENT;
-    for (const hm_batch *x : {cond, a, b, (const hm_batch *)out})
-        if (hm_status st = check_batch(x); st) return st;
-    if (cond->nbits != 8 || cond->n != a->n || b->nbits != a->nbits || b->n != a->n ||
-        out->nbits != a->nbits || out->n != a->n)
-        return HM_ERR_INVALID_ARGUMENT;
+    if (hm_status st = check_operands({{cond, 8}, {a, 0}, {b, 0}, {out, 0}}); st) return st;
     if (hm_status st = hm_validate_operation(c, HM_OP_SELECT, nullptr); st) return st;
     const uint32_t L = a->nbits;
     std::vector<uint32_t> need(L);
@@ -1233,25 +1092,14 @@ hm_status hm_select_batch(hm_ctx *c, const hm_batch *cond, const hm_batch *a, co
     if (!covers(out, need) || overlaps(out, cond) || overlaps(out, a) || overlaps(out, b))
         return HM_ERR_INVALID_ARGUMENT;
     if (a->n == 0) return HM_OK;
-    uint32_t SA = 2, SB = 2;
-    for (uint32_t i = 0; i < L; ++i) {
-        SA = std::max(SA, 2 * cap_of(a->bound[i]));
-        SB = std::max(SB, 2 * cap_of(b->bound[i]));
-    }
-    const uint32_t SX = std::max(SA, SB), SC = 2 * cap_of(cond->bound[0]);
+    const Slots s = operand_slots(a, b);
+    const uint32_t SC = 2 * cap_of(cond->bound[0]);
     SelectArgs G{};
     // c | a_i | b_i | x_i | the product c x_i + b_i: words(c) + words(x_i) <= SC + SX words
-    G.oC = 0, G.oA = SC + 2, G.oB = G.oA + SA + 2, G.oX = G.oB + SB + 2, G.oT = G.oX + SX + 2;
-    G.lds_per_wave = G.oT + SC + SX + 2;
-    if ((size_t)G.lds_per_wave * 16 > 160 * 1024) return HM_ERR_UNSUPPORTED;
-    G.cond = batch_arg(cond), G.a = batch_arg(a), G.b = batch_arg(b), G.out = batch_arg(out);
-    G.n = a->n, G.nbits = L, G.cbound = cond->bound[0];
-    G.status = c->d_status;
-    fill_bounds(G.ab, a);
-    fill_bounds(G.bb, b);
-    fill_bounds(G.ob, out);
-    DeviceGuard g(c->device);
-    return launch_select(G, c->stream) ? hip_fail(c, hipGetLastError()) : HM_OK;
+    G.oC = 0, G.oA = SC + 2, G.oB = G.oA + s.SA + 2, G.oX = G.oB + s.SB + 2, G.oT = G.oX + s.SX + 2;
+    G.lds_per_wave = G.oT + SC + s.SX + 2;
+    G.cond = batch_arg(cond), G.cbound = cond->bound[0];
+    return run_circuit(c, G, G.lds_per_wave, a, b, out, launch_select);
 } HM_ABI_CATCH
 
 // ------------------------------------------------------------------ polynomial primitives

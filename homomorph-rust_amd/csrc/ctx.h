@@ -1,5 +1,5 @@
 // ctx.h — internal to the engine library: the context object behind hm_ctx* and the host helpers
-// shared by capi.cpp and mul_host.cpp.  Not part of the ABI.
+// shared by capi.cpp, add_host.h and mul_host.cpp.  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,5 +1,6 @@
 // engine.h — argument blocks shared by the HIP kernels (kernels.hip) and the C-ABI host code
-// (capi.cpp).  Plain structs passed to kernels by value.
+// (capi.cpp; the adder's plan fields are filled by add_host.h, the multiplier's by
+// mul_host.cpp).  Plain structs passed to kernels by value.
 #pragma once
 #include <stdint.h>
 
@@ -57,7 +58,7 @@ struct AddArgs {
     uint32_t staged;                  // chain: x, ab, P and degrees staged in LDS, carry in place
     uint32_t cw;                      // chain: carry buffer words
     uint32_t max_prod_words;          // widest carry product along the chain (picks WMAX)
-    uint32_t pad;                     // carry buffers zero-padded: unchecked window reads (see capi)
+    uint32_t pad;                     // carry buffers zero-padded: unchecked window reads (add_host)
     uint32_t mfma;                    // chain on the matrix cores (adder_mfma.hip): its chunk count
                                       // NC (MfmaCfg), 0 = the VALU chain
     uint32_t mf_cw;                   // MFMA chain: carry bit words (tiles, window overhang)
@@ -123,6 +124,12 @@ struct GateArgs {
 //   kBorrowLt   the same borrows through bit nbits - 1; the result is w_nbits (+ 1 when flip)
 //   kBorrowEq   e_{i+1} = p_i e_i from e_0 = 1; the result is e_nbits (+ 1 when flip)
 enum { kBorrowSub = 0, kBorrowLt = 1, kBorrowEq = 2 };
+// A wave's LDS slice on that chain, word offsets (capi.cpp borrow_layout):
+// a_i | b_i | x_i | p_i | generate term | two borrow buffers of cw words each at oW
+struct BorrowLayout {
+    uint32_t lds_per_wave, oA, oB, oX, oP, oG, oW;
+    uint32_t cw;
+};
 struct BorrowArgs {
     int mode;          // kBorrowSub / kBorrowLt / kBorrowEq
     uint32_t flip;     // comparisons: the result plus the unit polynomial (>=, <=, !=)
@@ -130,14 +137,13 @@ struct BorrowArgs {
     BatchArg a, b, out;
     uint64_t n;
     uint32_t nbits;    // input bits (a comparison's output has 8)
-    uint32_t lds_per_wave, oA, oB, oX, oP, oG, oW; // word offsets in a wave's LDS slice
-    uint32_t cw;       // words of each of the two borrow buffers at oW
+    BorrowLayout lay;
     int *status;
     Bounds ab, bb, ob;
 };
 
 // min / max on the same chain (kernels.hip minmax_kernel), one wavefront per
-// value in the LDS layout of BorrowArgs.  Phase 1 is the kBorrowLt chain: it leaves w_nbits (the
+// value in the same BorrowLayout.  Phase 1 is the kBorrowLt chain: it leaves w_nbits (the
 // polynomial a < b returns) in one borrow buffer.  Phase 2 walks the bits again:
 //   min  out_i = b_i + w_nbits x_i      max  out_i = a_i + w_nbits x_i      (x = a + b)
 // each product formed into the other borrow buffer and stored from there.
@@ -147,8 +153,7 @@ struct MinMaxArgs {
     BatchArg a, b, out;
     uint64_t n;
     uint32_t nbits;
-    uint32_t lds_per_wave, oA, oB, oX, oP, oG, oW; // as BorrowArgs
-    uint32_t cw;       // words of each borrow buffer: the widest of p_i w_i and x_i w_nbits
+    BorrowLayout lay;  // cw: the widest of p_i w_i and x_i w_nbits
     int *status;
     Bounds ab, bb, ob;
 };

@@ -2,7 +2,8 @@
 //   gate_kernel     elementwise AND/OR/XOR/NOT (common.rs:5-35)
 //   borrow_kernel   subtraction, ==, !=, <, <=, >, >= as one ripple-borrow chain (no reference
 //                   circuit: DESIGN.md s4.4a)
-//   minmax_kernel   min / max: that chain's last borrow times a_i + b_i, in one launch (s4.4b)
+//   minmax_kernel   min / max: that chain (borrow_step, shared with borrow_kernel), then its last
+//                   borrow times a_i + b_i, in one launch (s4.4b)
 //   select_kernel   cond ? a : b on an encrypted bool (s4.4b)
 //   poly_* kernels single-polynomial primitives for unit parity (polynomial.rs:190-365)
 // (adder: adder.hip; cipher: cipher.hip; carry-save multiplier: mul_engine.hip)
@@ -11,6 +12,19 @@
 #include "dev_common.h"
 
 namespace hm {
+
+// The launch of the wave-per-value circuits (gates, borrow chain, min / max, select): one
+// wavefront per value, 4 per block, lds_per_wave words of dynamic LDS each.
+template <class Args>
+static int launch_wave_per_value(void (*kernel)(Args), const Args &g, uint32_t lds_per_wave,
+                                 void *stream) {
+    const int wpb = 4;
+    const uint64_t blocks = (g.n + wpb - 1) / wpb;
+    if (blocks == 0) return 0;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * wpb),
+                       (size_t)lds_per_wave * 4 * wpb, (hipStream_t)stream, g);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
 
 // ---------------------------------------------------------------------------------------------
 // Elementwise gates: one wavefront per value, bit by bit through LDS.
@@ -61,12 +75,7 @@ __global__ void __launch_bounds__(256) gate_kernel(GateArgs G) {
 }
 
 int launch_gate(const GateArgs &g, void *stream) {
-    const int wpb = 4;
-    const uint64_t blocks = (g.n + wpb - 1) / wpb;
-    if (blocks == 0) return 0;
-    hipLaunchKernelGGL(gate_kernel, dim3((unsigned)blocks), dim3(64 * wpb),
-                       (size_t)g.lds_per_wave * 4 * wpb, (hipStream_t)stream, g);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launch_wave_per_value(gate_kernel, g, g.lds_per_wave, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -91,15 +100,34 @@ __device__ __forceinline__ void xor_and_not(const uint32_t *A, int na, const uin
     *np = words_of(wave_max_i32(ldp));
 }
 
+// One step of the chain, w_{i+1} = g_i + p_i w_i into Wn (the caller then exchanges W and Wn);
+// returns its words.  generate: g_i = a_i b_i + b_i (not a and b), formed in Gt; when top, the
+// signed top bit, the operands' roles are exchanged: a_i b_i + a_i.  Otherwise g_i = 0 (the
+// equality prefix).  Shared by borrow_kernel and minmax_kernel's phase 1.
+__device__ __forceinline__ int borrow_step(const uint32_t *Ab, int na, const uint32_t *Bb, int nb,
+                                           const uint32_t *P, int np, const uint32_t *W, int nw,
+                                           uint32_t *Gt, uint32_t *Wn, bool generate, bool top) {
+    int ng = 0, nout;
+    if (generate) {
+        ng = words_of(wave_mul<kQSmall, 8>(Ab, na, Bb, nb, top ? Ab : Bb, top ? na : nb, Gt,
+                                           &nout));
+        wsync();
+    }
+    nw = words_of(wave_mul<kQSmall, 8>(P, np, W, nw, Gt, ng, Wn, &nout));
+    wsync();
+    return nw;
+}
+
 __global__ void __launch_bounds__(256) borrow_kernel(BorrowArgs G) {
     extern __shared__ uint32_t lds[];
     const int wave = (int)rfl(threadIdx.x >> 6); // wave-uniform by construction
     const uint64_t e = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave;
     if (e >= G.n) return;
     const int lane = lane_id();
-    uint32_t *L = lds + (size_t)wave * G.lds_per_wave;
-    uint32_t *Ab = L + G.oA, *Bb = L + G.oB, *X = L + G.oX, *P = L + G.oP, *Gt = L + G.oG;
-    uint32_t *W = L + G.oW, *Wn = W + G.cw;
+    const BorrowLayout &Y = G.lay;
+    uint32_t *L = lds + (size_t)wave * Y.lds_per_wave;
+    uint32_t *Ab = L + Y.oA, *Bb = L + Y.oB, *X = L + Y.oX, *P = L + Y.oP, *Gt = L + Y.oG;
+    uint32_t *W = L + Y.oW, *Wn = W + Y.cw;
     const uint64_t *pa = G.a.limbs + e * G.a.stride;
     const uint64_t *pb = G.b.limbs + e * G.b.stride;
     uint64_t *po = G.out.limbs + e * G.out.stride;
@@ -113,7 +141,7 @@ __global__ void __launch_bounds__(256) borrow_kernel(BorrowArgs G) {
         const int na = load_bit(pa + offa, rfl(G.a.degree[e * G.nbits + i]), G.ab.b[i], Ab, G.status);
         const int nb = load_bit(pb + offb, rfl(G.b.degree[e * G.nbits + i]), G.bb.b[i], Bb, G.status);
         wsync();
-        int nx, np, nout;
+        int nx, np;
         xor_and_not(Ab, na, Bb, nb, X, P, &nx, &np);
         wsync();
         if (G.mode == kBorrowSub) {
@@ -122,17 +150,8 @@ __global__ void __launch_bounds__(256) borrow_kernel(BorrowArgs G) {
             offo += cap_of(G.ob.b[i]);
             if (i + 1 == G.nbits) break; // the last borrow is not needed
         }
-        int ng = 0;
-        if (G.mode != kBorrowEq) {
-            // generate: a_i b_i + b_i (not a and b); the signed top bit has the operands' roles
-            // exchanged, a_i b_i + a_i
-            const bool top = G.sgn && i + 1 == G.nbits;
-            ng = words_of(wave_mul<kQSmall, 8>(Ab, na, Bb, nb, top ? Ab : Bb, top ? na : nb, Gt,
-                                               &nout));
-            wsync();
-        }
-        nw = words_of(wave_mul<kQSmall, 8>(P, np, W, nw, Gt, ng, Wn, &nout));
-        wsync();
+        const bool top = G.sgn && i + 1 == G.nbits;
+        nw = borrow_step(Ab, na, Bb, nb, P, np, W, nw, Gt, Wn, G.mode != kBorrowEq, top);
         uint32_t *t = W;
         W = Wn, Wn = t;
         offa += cap_of(G.ab.b[i]);
@@ -152,26 +171,21 @@ __global__ void __launch_bounds__(256) borrow_kernel(BorrowArgs G) {
 }
 
 int launch_borrow(const BorrowArgs &g, void *stream) {
-    const int wpb = 4;
-    const uint64_t blocks = (g.n + wpb - 1) / wpb;
-    if (blocks == 0) return 0;
-    hipLaunchKernelGGL(borrow_kernel, dim3((unsigned)blocks), dim3(64 * wpb),
-                       (size_t)g.lds_per_wave * 4 * wpb, (hipStream_t)stream, g);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launch_wave_per_value(borrow_kernel, g, g.lay.lds_per_wave, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
 // min / max (MinMaxArgs): the kBorrowLt chain above, then out_i = b_i + w_n x_i
-// (min) or a_i + w_n x_i (max) with w_n kept in LDS.  The chain step is written again here so that
-// borrow_kernel's code stays as it is.
+// (min) or a_i + w_n x_i (max) with w_n kept in LDS.
 __global__ void __launch_bounds__(256) minmax_kernel(MinMaxArgs G) {
     extern __shared__ uint32_t lds[];
     const int wave = (int)rfl(threadIdx.x >> 6); // wave-uniform by construction
     const uint64_t e = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave;
     if (e >= G.n) return;
-    uint32_t *L = lds + (size_t)wave * G.lds_per_wave;
-    uint32_t *Ab = L + G.oA, *Bb = L + G.oB, *X = L + G.oX, *P = L + G.oP, *Gt = L + G.oG;
-    uint32_t *W = L + G.oW, *Wn = W + G.cw;
+    const BorrowLayout &Y = G.lay;
+    uint32_t *L = lds + (size_t)wave * Y.lds_per_wave;
+    uint32_t *Ab = L + Y.oA, *Bb = L + Y.oB, *X = L + Y.oX, *P = L + Y.oP, *Gt = L + Y.oG;
+    uint32_t *W = L + Y.oW, *Wn = W + Y.cw;
     const uint64_t *pa = G.a.limbs + e * G.a.stride;
     const uint64_t *pb = G.b.limbs + e * G.b.stride;
     uint64_t *po = G.out.limbs + e * G.out.stride;
@@ -185,12 +199,7 @@ __global__ void __launch_bounds__(256) minmax_kernel(MinMaxArgs G) {
         int nx, np;
         xor_and_not(Ab, na, Bb, nb, X, P, &nx, &np);
         wsync();
-        const bool top = G.sgn && i + 1 == G.nbits; // the signed top bit generates a_i b_i + a_i
-        const int ng = words_of(wave_mul<kQSmall, 8>(Ab, na, Bb, nb, top ? Ab : Bb, top ? na : nb,
-                                                     Gt, &nout));
-        wsync();
-        nw = words_of(wave_mul<kQSmall, 8>(P, np, W, nw, Gt, ng, Wn, &nout));
-        wsync();
+        nw = borrow_step(Ab, na, Bb, nb, P, np, W, nw, Gt, Wn, true, G.sgn && i + 1 == G.nbits);
         uint32_t *t = W;
         W = Wn, Wn = t;
         offa += cap_of(G.ab.b[i]);
@@ -217,12 +226,7 @@ __global__ void __launch_bounds__(256) minmax_kernel(MinMaxArgs G) {
 }
 
 int launch_minmax(const MinMaxArgs &g, void *stream) {
-    const int wpb = 4;
-    const uint64_t blocks = (g.n + wpb - 1) / wpb;
-    if (blocks == 0) return 0;
-    hipLaunchKernelGGL(minmax_kernel, dim3((unsigned)blocks), dim3(64 * wpb),
-                       (size_t)g.lds_per_wave * 4 * wpb, (hipStream_t)stream, g);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launch_wave_per_value(minmax_kernel, g, g.lay.lds_per_wave, stream);
 }
 
 // Oblivious choice (SelectArgs): out_i = b_i + c x_i, c loaded once per value.
@@ -260,12 +264,7 @@ __global__ void __launch_bounds__(256) select_kernel(SelectArgs G) {
 }
 
 int launch_select(const SelectArgs &g, void *stream) {
-    const int wpb = 4;
-    const uint64_t blocks = (g.n + wpb - 1) / wpb;
-    if (blocks == 0) return 0;
-    hipLaunchKernelGGL(select_kernel, dim3((unsigned)blocks), dim3(64 * wpb),
-                       (size_t)g.lds_per_wave * 4 * wpb, (hipStream_t)stream, g);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launch_wave_per_value(select_kernel, g, g.lds_per_wave, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -167,7 +167,8 @@ def mul_bounds(ba, bb):
 
 
 def add_plan(ba, bb):
-    """hm_add_batch's sizing (capi.cpp), restated: cntX, maxPw, SC and what follows from them."""
+    """plan_add's sizing (add_host.h), restated as an independent model: cntX, maxPw, SC and what
+    follows from them (check_add_path holds the planner's own census against it)."""
     wob = lambda b: 0 if b < 0 else b // 32 + 1  # noqa: E731  words_of_bound
     L = len(ba)
     cntX, SC, maxPw, cntAB, cb = 1, 2, 0, 1, -1
@@ -499,33 +500,46 @@ def mul_class_reference(name):
 
 # ------------------------------------------------------------------ the planner's census
 @functools.lru_cache(maxsize=None)
-def _census_driver():
-    """Builds tests/sanitize/_build/plan_census (the planner compiled into a host-only driver,
-    ASan + UBSan) once per process."""
+def _census_driver(name="plan_census"):
+    """Builds tests/sanitize/_build/<name> (a planner compiled into a host-only driver, ASan +
+    UBSan) once per process."""
     import os
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    subprocess.run(["make", "-s", "-C", os.path.join(root, "homomorph-rust_amd")], check=True,
-                   timeout=1200)
     san = os.path.join(root, "tests", "sanitize")
-    subprocess.run(["make", "-s", "-C", san, "_build/plan_census"], check=True, timeout=1200)
-    return os.path.join(san, "_build", "plan_census")
+    if name != "add_census":  # (plan_census links the library's objects; add_census nothing)
+        subprocess.run(["make", "-s", "-C", os.path.join(root, "homomorph-rust_amd")], check=True,
+                       timeout=1200)
+    subprocess.run(["make", "-s", "-C", san, "_build/" + name], check=True, timeout=1200)
+    return os.path.join(san, "_build", name)
+
+
+def _run_census(name, args):
+    import json
+    import os
+    import subprocess
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0",
+               UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([_census_driver(name)] + [str(int(x)) for x in args], capture_output=True,
+                       text=True, timeout=300, env=env)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    return json.loads(r.stdout)
 
 
 @functools.lru_cache(maxsize=None)
 def plan_census(L, K, signed, ka_min, ka_leaf, mfma, ba, bb):
     """The planner's own account of one plan (tests/sanitize/plan_census.cpp), as a dict.  CPU
     only.  Any sanitizer report fails the run."""
-    import json
-    import os
-    import subprocess
-    args = [L, K, int(signed), ka_min, ka_leaf, int(mfma)] + list(ba) + list(bb)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0",
-               UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([_census_driver()] + [str(int(x)) for x in args], capture_output=True,
-                       text=True, timeout=300, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return json.loads(r.stdout)
+    return _run_census("plan_census",
+                       [L, K, int(signed), ka_min, ka_leaf, int(mfma)] + list(ba) + list(bb))
+
+
+@functools.lru_cache(maxsize=None)
+def add_census(n, add_chain, fp4, ba, bb):
+    """plan_add's own account of one adder plan (tests/sanitize/add_census.cpp), as a dict:
+    "status", and when it is 0 every plan field of AddArgs and the kernel instances.  ba, bb:
+    tuples of per-bit bounds.  CPU only.  Any sanitizer report fails the run."""
+    return _run_census("add_census", [len(ba), n, add_chain, int(fp4)] + list(ba) + list(bb))
 
 
 def mul_census(name, mfma=True):
@@ -612,10 +626,17 @@ def check_borrow_path(name):
 
 
 def check_add_path(name):
-    """hm_add_batch's plan limits (capi.cpp: maxPw <= 2 NC - 1, cntX <= 32, PAD: maxPw <= 25,
+    """hm_add_batch's plan limits (add_host.h: maxPw <= 2 NC - 1, cntX <= 32, PAD: maxPw <= 25,
     wmax from need_w = ceil(SC / 64)) and data that reaches them."""
     c = inputs("add", name)
     plan = add_plan(c["ba"], c["bb"])
+    # the planner's own output (AUTO chain on a device with the fp4 MFMA, the batch as the GPU
+    # tier runs it) agrees with the model on every field they share
+    cen = add_census(len(c["A"]), 0, True, tuple(int(x) for x in c["ba"]),
+                     tuple(int(x) for x in c["bb"]))
+    assert cen["status"] == 0
+    assert (cen["cntX"], cen["cntP"], cen["max_prod_words"], bool(cen["pad"]), cen["mfma"]) == (
+        plan["cntX"], plan["maxPw"], plan["SC"], plan["pad"], plan["nc"]), (cen, plan)
     tr = [add_trace(a, b) for a, b in zip(c["A"], c["B"])]
     rows = [r for t in tr for r in t]
     npw, nx, nprod = (max(r[k] for r in rows) for k in ("np", "nx", "nprod"))

@@ -10,6 +10,8 @@ engine library's host code, run on the CPU (GPU sanitizers are not available on 
   same leaf products as the breadth-first plans at K = 16, K = 21 planned;
 - tests/sanitize/plan_census.cpp: one plan's launches and sizes as JSON (host only), the source of
   the full-bounds tier's multiplier path assertions (tests/synth.py mul_census);
+- tests/sanitize/add_census.cpp: one adder plan (add_host.h plan_add) as JSON, the planner
+  compiled alone into the driver (tests/synth.py add_census, tests/test_add_plans.py);
 - tests/sanitize/capi_oom.cpp (not sanitised): every allocation inside the multiplier's plan
   builder failed in turn, each call returning HM_ERR_OUT_OF_MEMORY instead of throwing across
   the C ABI.
@@ -75,4 +77,33 @@ def test_plan_census_under_asan_ubsan(built):
     assert sum(len(col["ka"]) for col in cen["cols"]) == 5
     r = subprocess.run([exe, "8", "4", "0", "256", "256", "1", "640"], capture_output=True,
                        text=True, timeout=300, env=env)
+    assert r.returncode == 2 and "expected" in r.stderr
+
+
+def test_add_census_under_asan_ubsan(built):
+    """tests/sanitize/add_census.cpp (the driver behind synth.add_census): the headline plan (u8,
+    bounds 256, 131072 values: the uniform prep and the NC = 13 MFMA chain), the same on the VALU
+    chain, a refused plan and a refused argument list."""
+    import json
+    exe = os.path.join(built, "add_census")
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0",
+               UBSAN_OPTIONS="print_stacktrace=1")
+
+    def run(*args):
+        return subprocess.run([exe] + [str(x) for x in args], capture_output=True, text=True,
+                              timeout=300, env=env)
+    r = run(8, 131072, 0, 1, *[256] * 16)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    cen = json.loads(r.stdout)
+    assert cen["status"] == 0 and cen["ucap"] == 5 and cen["mfma"] == 13
+    assert cen["prep_instance"] == "add_prep_uniform_kernel<5>"
+    assert cen["chain_instance"] == "add_chain_mfma_kernel<13>"
+    r = run(8, 131072, 2, 1, *[256] * 16)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    cen = json.loads(r.stdout)
+    assert cen["mfma"] == 0 and cen["mf_cw"] == 0 and cen["staged"] == 1
+    assert cen["chain_instance"] == "add_chain_staged_kernel<4>"
+    r = run(8, 64, 1, 0, *[256] * 16)  # an explicit MFMA chain without the fp4 MFMA
+    assert r.returncode == 0 and json.loads(r.stdout) == {"status": 7}
+    r = run(8, 64, 0, 1, 256)
     assert r.returncode == 2 and "expected" in r.stderr
