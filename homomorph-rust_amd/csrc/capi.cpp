@@ -4,7 +4,8 @@
 // call the way the reference's safe wrappers do (Context::validate_operation, src/context.rs:
 // 310-323; Parameters::new asserts, :87-94), computes static degree bounds and the per-wave LDS
 // carve-outs of the wave-per-value circuits, and launches the kernels.  The adder's plan comes
-// from add_host.h (plan_add), the multiplier's from mul_host.cpp.  Never throws across the ABI.
+// from add_host.h (plan_add), the multiplier's from mul_host.cpp, the table lookup's from
+// lookup_host.h (plan_lookup).  Never throws across the ABI.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -19,6 +20,7 @@
 
 #include "add_host.h"
 #include "ctx.h"
+#include "lookup_host.h"
 
 using namespace hm;
 
@@ -106,8 +108,8 @@ uint16_t min_d_over_delta(hm_op op) { // src/impls/numbers.rs:27-50
     case HM_OP_ADD: return 21;
     case HM_OP_MUL: case HM_OP_MUL_SIGNED: return 64;
     case HM_OP_SELECT: return 5; // 2m + 1 for c x_i of fresh bits, m = 2
-    default: break; // HM_OP_SUB .. HM_OP_GE, HM_OP_MIN, HM_OP_MAX depend on the width:
-                    // borrow_min_d_over_delta
+    default: break; // HM_OP_SUB .. HM_OP_GE, HM_OP_MIN, HM_OP_MAX, HM_OP_LOOKUP depend on the
+                    // width: borrow_min_d_over_delta
     }
     return 0xFFFF;
 }
@@ -116,12 +118,13 @@ bool is_borrow_op(hm_op op) { return op >= HM_OP_SUB && op <= HM_OP_GE; }
 bool is_compare_op(hm_op op) { return op >= HM_OP_EQ && op <= HM_OP_GE; }
 bool is_ordering_op(hm_op op) { return op >= HM_OP_LT && op <= HM_OP_GE; }
 bool is_minmax_op(hm_op op) { return op == HM_OP_MIN || op == HM_OP_MAX; }
-bool needs_width(hm_op op) { return is_borrow_op(op) || is_minmax_op(op); }
+bool needs_width(hm_op op) { return is_borrow_op(op) || is_minmax_op(op) || op == HM_OP_LOOKUP; }
 
 // 2m + 1 with m the borrow circuit's degree in fresh input bits: nbits + 1 for the orderings
 // (the borrow out of the top bit), nbits for subtraction and equality, nbits + 2 for min / max
-// (that borrow times x_i).  A fresh bit's noise has degree delta + 1 <= 2 delta, so
-// d >= (2m + 1) delta gives m (delta + 1) < d.
+// (that borrow times x_i).  A table lookup is multilinear in its nbits index bits: m = nbits.
+// A fresh bit's noise has degree delta + 1 <= 2 delta, so d >= (2m + 1) delta gives
+// m (delta + 1) < d.
 uint16_t borrow_min_d_over_delta(hm_op op, uint32_t nbits) {
     const uint32_t m = nbits + (is_ordering_op(op) ? 1u : is_minmax_op(op) ? 2u : 0u);
     return (uint16_t)(2 * m + 1);
@@ -774,6 +777,18 @@ hm_status hm_select_out_bounds(uint32_t L, uint32_t cond_bound0, const uint32_t 
     return choice_bounds(L, cond_bound0, a, b, out);
 } HM_ABI_CATCH
 
+// Degree bounds of a table lookup: per output bit the widest monomial of its
+// algebraic normal form.
+hm_status hm_lookup_out_bounds(uint32_t in_bits, const uint32_t *a, const uint8_t *table,
+                               uint32_t out_nbytes, uint32_t *out) try {
+    if (!a || !table || !out || in_bits == 0 || in_bits > kLookupMaxIn ||
+        (out_nbytes != 1 && out_nbytes != 2 && out_nbytes != 4))
+        return HM_ERR_INVALID_ARGUMENT;
+    uint32_t coef[kLookupMaxOut][8];
+    lookup_plan::moebius(in_bits, table, out_nbytes, coef);
+    return lookup_plan::bounds(in_bits, a, coef, 8 * out_nbytes, out);
+} HM_ABI_CATCH
+
 hm_status hm_minmax_out_bounds(uint32_t L, const uint32_t *a, const uint32_t *b,
                                uint32_t *out) try {
     if (!a || !b || !out || L == 0 || L > HM_MAX_BITS) return HM_ERR_INVALID_ARGUMENT;
@@ -1100,6 +1115,31 @@ hm_status hm_select_batch(hm_ctx *c, const hm_batch *cond, const hm_batch *a, co
     G.lds_per_wave = G.oT + SC + s.SX + 2;
     G.cond = batch_arg(cond), G.cbound = cond->bound[0];
     return run_circuit(c, G, G.lds_per_wave, a, b, out, launch_select);
+} HM_ABI_CATCH
+
+hm_status hm_lookup_batch(hm_ctx *c, const hm_batch *a, uint32_t in_bits, const uint8_t *table,
+                          uint32_t out_nbytes, hm_batch *out) try {
+    if (!c || !a || !table || !out) return HM_ERR_INVALID_ARGUMENT;
+    if (hm_status st = check_batch(a); st) return st;
+    if (hm_status st = check_batch(out); st) return st;
+    if (in_bits == 0 || in_bits > kLookupMaxIn || in_bits > a->nbits ||
+        (out_nbytes != 1 && out_nbytes != 2 && out_nbytes != 4) || out->nbits != 8 * out_nbytes ||
+        out->n != a->n)
+        return HM_ERR_INVALID_ARGUMENT;
+    if (hm_status st = hm_validate_operation_bits(c, HM_OP_LOOKUP, in_bits, nullptr); st) return st;
+    LookupArgs G{};
+    lookup_plan::moebius(in_bits, table, out_nbytes, G.coef);
+    std::vector<uint32_t> need(out->nbits);
+    if (hm_status st = lookup_plan::bounds(in_bits, a->bound, G.coef, out->nbits, need.data()); st)
+        return st;
+    if (!covers(out, need) || overlaps(out, a)) return HM_ERR_INVALID_ARGUMENT;
+    if (a->n == 0) return HM_OK;
+    if (hm_status st = plan_lookup(in_bits, a->bound, out_nbytes, G); st) return st;
+    G.a = batch_arg(a), G.out = batch_arg(out);
+    G.n = a->n, G.status = c->d_status;
+    for (uint32_t j = 0; j < out->nbits; ++j) G.ob[j] = out->bound[j];
+    DeviceGuard g(c->device);
+    return launch_lookup(G, c->stream) ? hip_fail(c, hipGetLastError()) : HM_OK;
 } HM_ABI_CATCH
 
 // ------------------------------------------------------------------ polynomial primitives

@@ -171,6 +171,34 @@ struct SelectArgs {
     Bounds ab, bb, ob;
 };
 
+// Table lookup (kernels.hip lookup_kernel): out = T[v] for the k <= 8 low bits v
+// of a value and a plaintext table T, as the algebraic normal form of every output bit,
+//   out_j = sum over the sets S with coef[j] bit S of prod_{i in S} a_i,
+// one wavefront per value.  The index bits are split into a low half (kl = ceil(k / 2) bits) and a
+// high half (kh bits); the monomials of either half are formed once per value by doubling
+// (M[s | 1 << i] = M[s] a_i), then out_j = sum_t MH[t] I_jt with the inner sums
+// I_jt = sum_s coef[j][t 2^kl + s] ML[s] plain XORs: at most 2^kh - 1 products per output bit.
+// Everything below is filled by lookup_host.h plan_lookup.  A monomial's index is s for the low
+// half and 16 + t for the high half (off, need and the word counts at oN); ML[0] = MH[0] = the unit
+// polynomial, one shared word.  The coefficient masks travel by value: every index into them, as
+// into off, ab and ob, is wave-uniform (dev_common.h).
+constexpr uint32_t kLookupMaxIn = 8;   // index bits
+constexpr uint32_t kLookupMaxOut = 32; // output bits
+struct LookupArgs {
+    BatchArg a, out;
+    uint64_t n;
+    uint32_t k, kl, kh;  // index bits: all, low half, high half
+    uint32_t nob;        // output bits
+    uint32_t need;       // monomials some output bit uses (with the ones they are formed from)
+    // word offsets in a wave's LDS slice: the monomials' word counts (32 words) | the unit | the
+    // monomials | an inner sum of cI words | two accumulators of cP words each
+    uint32_t lds_per_wave, oN, oI, oP, cI, cP;
+    uint32_t off[32];
+    uint32_t coef[kLookupMaxOut][8]; // bit S of coef[j]: the monomial of the index bits in S
+    uint32_t ab[kLookupMaxIn], ob[kLookupMaxOut];
+    int *status;
+};
+
 // Column-parallel carry-save multiplier (mul_engine.hip, mul_host.cpp).  Column i of
 // mul_unsigned_internal (common.rs:66-105) XORs its items x_0..x_{n-1} (the partial products
 // a_j b_{i-j}, then the previous column's carries) into result_i and pushes the carry
@@ -453,6 +481,7 @@ int launch_gate(const GateArgs &a, void *stream);
 int launch_borrow(const BorrowArgs &a, void *stream);
 int launch_minmax(const MinMaxArgs &a, void *stream);
 int launch_select(const SelectArgs &a, void *stream);
+int launch_lookup(const LookupArgs &a, void *stream);
 int launch_mul_stage(const MulStageArgs &a, void *stream);
 int launch_mul_pp(const MulPPArgs &a, void *stream);
 int launch_mul_scan(const MulScanArgs &a, void *stream);

@@ -5,6 +5,7 @@
 //   minmax_kernel   min / max: that chain (borrow_step, shared with borrow_kernel), then its last
 //                   borrow times a_i + b_i, in one launch (s4.4b)
 //   select_kernel   cond ? a : b on an encrypted bool (s4.4b)
+//   lookup_kernel   T[v] for a plaintext table T and an encrypted index of up to 8 bits (s4.4c)
 //   poly_* kernels single-polynomial primitives for unit parity (polynomial.rs:190-365)
 // (adder: adder.hip; cipher: cipher.hip; carry-save multiplier: mul_engine.hip)
 #include <hip/hip_runtime.h>
@@ -13,7 +14,7 @@
 
 namespace hm {
 
-// The launch of the wave-per-value circuits (gates, borrow chain, min / max, select): one
+// The launch of the wave-per-value circuits (gates, borrow chain, min / max, select, lookup): one
 // wavefront per value, 4 per block, lds_per_wave words of dynamic LDS each.
 template <class Args>
 static int launch_wave_per_value(void (*kernel)(Args), const Args &g, uint32_t lds_per_wave,
@@ -265,6 +266,101 @@ __global__ void __launch_bounds__(256) select_kernel(SelectArgs G) {
 
 int launch_select(const SelectArgs &g, void *stream) {
     return launch_wave_per_value(select_kernel, g, g.lds_per_wave, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Table lookup (LookupArgs): out_j = sum_t MH[t] I_jt over the monomials of the
+// index bits' low and high halves, I_jt = the XOR of the low monomials the table's coefficient
+// mask names.  The masks are plaintext, so every skip below is a scalar branch.
+
+// Dst[0..cI) = the XOR of the monomials M[s] (s: the set bits of m) at their word counts N[s];
+// returns its words.
+__device__ __forceinline__ int lookup_inner_sum(const LookupArgs &G, const uint32_t *L,
+                                                const uint32_t *N, uint32_t m, uint32_t *Dst) {
+    const int lane = lane_id();
+    int ldeg = -1;
+    for (uint32_t w0 = 0; w0 < G.cI; w0 += kWave) {
+        const uint32_t w = w0 + lane;
+        uint32_t v = 0u;
+        for (uint32_t mm = m; mm; mm &= mm - 1) {
+            const uint32_t s = (uint32_t)__builtin_ctz(mm);
+            if (w < rfl(N[s])) v ^= L[G.off[s] + w];
+        }
+        if (w < G.cI) Dst[w] = v;
+        if (v) ldeg = (int)w * 32 + 31 - __builtin_clz(v);
+    }
+    return words_of(wave_max_i32(ldeg));
+}
+
+__global__ void __launch_bounds__(256) lookup_kernel(LookupArgs G) {
+    extern __shared__ uint32_t lds[];
+    const int wave = (int)rfl(threadIdx.x >> 6); // wave-uniform by construction
+    const uint64_t e = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave;
+    if (e >= G.n) return;
+    const int lane = lane_id();
+    uint32_t *L = lds + (size_t)wave * G.lds_per_wave;
+    uint32_t *N = L + G.oN, *I = L + G.oI, *P = L + G.oP, *Pn = P + G.cP;
+    if (lane == 0) L[G.off[0]] = 1u, N[0] = 1u, N[16] = 1u; // ML[0] = MH[0] = 1
+    // every index bit once, into its monomial's slot
+    const uint64_t *pa = G.a.limbs + e * G.a.stride;
+    uint32_t offa = 0;
+    for (uint32_t i = 0; i < G.k; ++i) {
+        const uint32_t id = i < G.kl ? 1u << i : 16u + (1u << (i - G.kl));
+        const int na = load_bit(pa + offa, rfl(G.a.degree[e * G.a.dstride + i]), G.ab[i],
+                                L + G.off[id], G.status);
+        if (lane == 0) N[id] = (uint32_t)na;
+        offa += cap_of(G.ab[i]);
+    }
+    wsync();
+    // the other monomials by doubling: M[s | 1 << i] = a_i M[s], a_i the uniform operand
+    int nout;
+    for (uint32_t half = 0; half < 2; ++half) {
+        const uint32_t h = 16 * half;
+        for (uint32_t i = 1; i < (half ? G.kh : G.kl); ++i) {
+            const uint32_t nb = rfl(N[h + (1u << i)]);
+            for (uint32_t s = 1; s < (1u << i); ++s) {
+                const uint32_t id = h + (1u << i) + s;
+                if (!((G.need >> id) & 1u)) continue;
+                const int nm = words_of(wave_mul<kQSmall, 8>(L + G.off[h + (1u << i)], (int)nb,
+                                                             L + G.off[h + s], (int)rfl(N[h + s]),
+                                                             nullptr, 0, L + G.off[id], &nout));
+                if (lane == 0) N[id] = (uint32_t)nm;
+                wsync();
+            }
+        }
+    }
+    uint64_t *po = G.out.limbs + e * G.out.stride;
+    uint32_t offo = 0;
+    for (uint32_t j = 0; j < G.nob; ++j) {
+        int np = 0; // words of the accumulator P
+        for (uint32_t t = 0; t < (1u << G.kh); ++t) {
+            const uint32_t at = t << G.kl;
+            const uint32_t m = (G.coef[j][at >> 5] >> (at & 31)) & ((1u << (1u << G.kl)) - 1u);
+            if (!m) continue;
+            if (t == 0) { // MH[0] = 1: the inner sum itself
+                np = lookup_inner_sum(G, L, N, m, P);
+                wsync();
+                continue;
+            }
+            const int nh = (int)rfl(N[16 + t]);
+            if (!nh) continue;
+            const int ni = lookup_inner_sum(G, L, N, m, I);
+            wsync();
+            if (!ni) continue;
+            np = words_of(wave_mul<kQSmall, 8>(L + G.off[16 + t], nh, I, ni, P, np, Pn, &nout));
+            wsync();
+            uint32_t *x = P;
+            P = Pn, Pn = x;
+        }
+        store_xor_bit(P, np, nullptr, 0, po + offo, G.ob[j], G.out.degree + e * G.nob + j,
+                      G.status);
+        wsync();
+        offo += cap_of(G.ob[j]);
+    }
+}
+
+int launch_lookup(const LookupArgs &g, void *stream) {
+    return launch_wave_per_value(lookup_kernel, g, g.lds_per_wave, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

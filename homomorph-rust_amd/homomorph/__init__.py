@@ -31,12 +31,12 @@ __all__ = [
     "HomomorphicAddition", "HomomorphicMultiplication",
     "HomomorphicSubtraction", "HomomorphicEqual", "HomomorphicNotEqual", "HomomorphicLessThan",
     "HomomorphicLessEqual", "HomomorphicGreaterThan", "HomomorphicGreaterEqual",
-    "HomomorphicSelect", "HomomorphicMin", "HomomorphicMax",
+    "HomomorphicSelect", "HomomorphicMin", "HomomorphicMax", "HomomorphicLookup",
     "OperationError", "ContextCryptoError", "CipherError", "EngineError", "LibraryMissing",
     "EngineGraph",
     "add_out_bounds", "mul_out_bounds", "gate_out_bounds", "sub_out_bounds",
     "compare_out_bounds", "select_out_bounds", "minmax_out_bounds", "batch_stride", "caps",
-    "select_into", "minmax_into",
+    "select_into", "minmax_into", "lookup_out_bounds", "lookup_into",
 ]
 
 
@@ -112,16 +112,20 @@ class HomomorphicMultiplication(_Op):
     MIN_D_OVER_DELTA, CODE = 64, _lib.OP_MUL
 
 
-class _BorrowOp(_Op):
-    """The engine's ripple-borrow operations (no reference circuit).  Their
-    requirement depends on the width of the type: 2m + 1 with m the circuit's degree in fresh
-    input bits (EXTRA_DEGREE more than the width)."""
+class _WidthOp(_Op):
+    """An operation whose requirement depends on a width: 2m + 1 with m the circuit's degree in
+    fresh input bits (EXTRA_DEGREE more than the width).  Validated with nbits."""
     MIN_D_OVER_DELTA = None
     EXTRA_DEGREE = 0
 
     @classmethod
     def min_d_over_delta(cls, nbits: int) -> int:
         return 2 * (int(nbits) + cls.EXTRA_DEGREE) + 1
+
+
+class _BorrowOp(_WidthOp):
+    """The engine's ripple-borrow operations (no reference circuit): the width
+    is that of the type."""
 
 
 class HomomorphicSubtraction(_BorrowOp):
@@ -179,8 +183,20 @@ class HomomorphicSelect(_Op):
         return ctx.select(cond, a, b)
 
 
+class HomomorphicLookup(_WidthOp):
+    """table[a] for a plaintext table and an index of up to 8 encrypted bits: ctx.lookup(a, table)
+    (DESIGN.md s4.4c).  The width is the number of index bits (a byte: 17, a bool: 3), and the
+    requirement covers fresh index bits; an index that came out of another operation carries that
+    operation's depth."""
+    CODE = _lib.OP_LOOKUP
+
+
 def _is_borrow(op) -> bool:
     return isinstance(op, type) and issubclass(op, _BorrowOp)
+
+
+def _needs_width(op) -> bool:
+    return isinstance(op, type) and issubclass(op, _WidthOp)
 
 
 def _is_compare(op) -> bool:
@@ -323,6 +339,40 @@ def minmax_out_bounds(a_bound, b_bound) -> np.ndarray:
     out = np.zeros_like(a)
     _check(lib().hm_minmax_out_bounds(a.size, _p32(a), _p32(b), _p32(out)),
            "hm_minmax_out_bounds")
+    return out
+
+
+_TABLE_DTYPES = {np.dtype(t) for t in (np.bool_, np.uint8, np.int8, np.uint16, np.int16, np.uint32,
+                                        np.int32)}
+
+
+def _table_bytes(table, in_bits):
+    """(little-endian bytes of a lookup table, bytes per entry, its dtype, in_bits): a 1-D numpy
+    array of 2^in_bits entries of dtype bool, u8 / i8, u16 / i16 or u32 / i32."""
+    t = np.asarray(table)
+    if t.ndim != 1 or t.dtype not in _TABLE_DTYPES:
+        raise ValueError("a lookup table is a 1-D array of bool, (u)int8, (u)int16 or (u)int32")
+    if in_bits is None:
+        in_bits = max(int(t.size).bit_length() - 1, 0)
+    in_bits = int(in_bits)
+    if 0 <= in_bits <= 8 and t.size != 1 << in_bits:
+        raise ValueError(f"a table for {in_bits} index bits has {1 << in_bits} entries")
+    raw = np.ascontiguousarray(t.astype(t.dtype.newbyteorder("<"))).view(np.uint8).reshape(-1)
+    return raw, t.dtype.itemsize, t.dtype, in_bits
+
+
+def lookup_out_bounds(a_bound, table, in_bits=None) -> np.ndarray:
+    """hm_lookup_out_bounds: per-bit bounds of lookup(a, table) from the bounds of a's low
+    in_bits bits (default: as many as the table indexes) -- per output bit the widest monomial of
+    the table's algebraic normal form."""
+    raw, nbytes, _, in_bits = _table_bytes(table, in_bits)
+    a = _u32(a_bound)
+    if a.size < in_bits:
+        raise ValueError(f"{in_bits} index bits need as many input bounds")
+    a = np.ascontiguousarray(a[:max(in_bits, 0)])
+    out = np.zeros(8 * nbytes, dtype=np.uint32)
+    _check(lib().hm_lookup_out_bounds(in_bits, _p32(a), raw.ctypes.data_as(_lib.u8p), nbytes,
+                                      _p32(out)), "hm_lookup_out_bounds")
     return out
 
 
@@ -751,15 +801,16 @@ class Context:
     def validate_operation(self, op, nbits=None) -> None:
         """Context::validate_operation (src/context.rs:310-323).  Built-in operations ask the
         engine (hm_validate_operation); a user operation supplies MIN_D_OVER_DELTA itself.
-        Subtraction and the comparisons need the width of the type (nbits): their requirement
-        grows with it (hm_validate_operation_bits)."""
+        Subtraction, the comparisons, min / max and the table lookup need a width (nbits: of the
+        type, for the lookup of the index): their requirement grows with it
+        (hm_validate_operation_bits)."""
         if not hasattr(op, "CODE"):
             req = int(op.MIN_D_OVER_DELTA)
             if self._params.d < req * self._params.delta:
                 raise OperationError(req, self._params.d, self._params.delta)
             return
         req = ctypes.c_uint16()
-        if _is_borrow(op):
+        if _needs_width(op):
             if nbits is None:
                 raise ValueError(f"{op.__name__} is validated for a width: pass nbits")
             st = lib().hm_validate_operation_bits(self._h, op.CODE, int(nbits), ctypes.byref(req))
@@ -823,6 +874,24 @@ class Context:
         out = Ciphered.empty(a.n, need if out_bound is None else out_bound, self.device,
                              a.plain_dtype)
         select_into(self, cond, a, b, out)
+        return out
+
+    def lookup(self, a: Ciphered, table, in_bits=None, out_bound=None) -> Ciphered:
+        """table[v] per value (hm_lookup_batch), v the unsigned integer of a's low in_bits
+        ciphertext bits (default min(a.nbits, 8)): any function of an encrypted byte, nibble or
+        bool.  table: a numpy array of 2^in_bits entries of dtype bool, u8 / i8, u16 / i16 or
+        u32 / i32; the result's plaintext dtype is the table's.  For a signed input the index is
+        the bit pattern (v & 0xFF for an i8): entry 255 is the image of -1.  The table is
+        plaintext, and the output bounds depend on it (lookup_out_bounds)."""
+        if in_bits is None:
+            in_bits = min(a.nbits, 8)
+        raw, nbytes, dtype, in_bits = _table_bytes(table, in_bits)
+        if not 1 <= in_bits <= min(a.nbits, 8):
+            raise EngineError(_lib.ERR_INVALID_ARGUMENT, "lookup: in_bits")
+        self.validate_operation(HomomorphicLookup, in_bits)
+        need = lookup_out_bounds(a.bound, table, in_bits)
+        out = Ciphered.empty(a.n, need if out_bound is None else out_bound, self.device, dtype)
+        lookup_into(self, a, table, out, in_bits)
         return out
 
     def mul_plan_work(self, a_bound, b_bound, k=None, signed=False) -> float:
@@ -954,6 +1023,19 @@ def select_into(ctx: Context, cond: Ciphered, a: Ciphered, b: Ciphered, out: Cip
     ctx._launch(lambda: lib().hm_select_batch(ctx._h, ctypes.byref(cc), ctypes.byref(ca),
                                               ctypes.byref(cb), ctypes.byref(co)),
                 "hm_select_batch")
+
+
+def lookup_into(ctx: Context, a: Ciphered, table, out: Ciphered, in_bits=None) -> None:
+    """hm_lookup_batch into a preallocated output (bounds: lookup_out_bounds over a's low in_bits
+    bounds; in_bits defaults to min(a.nbits, 8)).  The table is read during the call: a graph
+    that captured it keeps the table it was captured with."""
+    if in_bits is None:
+        in_bits = min(a.nbits, 8)
+    raw, nbytes, _, in_bits = _table_bytes(table, in_bits)
+    ca, co = a._c(), out._c()
+    ctx._launch(lambda: lib().hm_lookup_batch(ctx._h, ctypes.byref(ca), in_bits,
+                                              raw.ctypes.data_as(_lib.u8p), nbytes,
+                                              ctypes.byref(co)), "hm_lookup_batch")
 
 
 def minmax_into(ctx: Context, op, a: Ciphered, b: Ciphered, out: Ciphered, signed=None) -> None:

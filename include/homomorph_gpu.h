@@ -34,12 +34,13 @@
 extern "C" {
 #endif
 
-#define HM_ABI_VERSION 7 /* 4: kernel timing by device stamps (HM_TIME_*), hm_ctx_last_hip_error;
+#define HM_ABI_VERSION 8 /* 4: kernel timing by device stamps (HM_TIME_*), hm_ctx_last_hip_error;
                             5: hm_ctx_clear_kernel_timing, hm_ctx_set_mul_scratch;
                             6: HM_OP_SUB .. HM_OP_GE, hm_sub_batch, hm_compare_batch, their bounds,
                                hm_validate_operation_bits;
                             7: HM_OP_SELECT, HM_OP_MIN, HM_OP_MAX, hm_select_batch,
-                               hm_minmax_batch, their bounds */
+                               hm_minmax_batch, their bounds;
+                            8: HM_OP_LOOKUP, hm_lookup_batch, hm_lookup_out_bounds */
 #define HM_MAX_BITS 128 /* u128 is the widest type with impls (src/impls/numbers/uint.rs:58) */
 
 typedef enum hm_status {
@@ -103,6 +104,10 @@ typedef enum hm_op {
     HM_OP_SELECT = 14,        /* HomomorphicSelect           cond ? a : b,  min d/delta 5 */
     HM_OP_MIN = 15,           /* HomomorphicMin              min(a, b) */
     HM_OP_MAX = 16,           /* HomomorphicMax              max(a, b) */
+    /* Any function of the n <= 8 low bits of a value, given as a plaintext table (hm_lookup_batch):
+     * a multilinear polynomial of degree at most n in those bits, so m = n and min d/delta 2n + 1
+     * (a byte 17, a bool 3): width dependent (hm_validate_operation_bits), for fresh index bits. */
+    HM_OP_LOOKUP = 17,        /* HomomorphicLookup           table[a] */
 } hm_op;
 
 typedef struct hm_ctx hm_ctx;
@@ -256,8 +261,10 @@ hm_status hm_validate_operation(const hm_ctx *ctx, hm_op op, uint16_t *required_
  * 2m + 1 above (u32: 65 for SUB / EQ / NE, 67 for the orderings), which gives m (delta + 1) < d,
  * so results on fresh inputs decrypt exactly; nbits outside 1..HM_MAX_BITS is
  * HM_ERR_INVALID_ARGUMENT.  HM_OP_MIN / HM_OP_MAX likewise: 2 nbits + 5 (u32: 69).
+ * HM_OP_LOOKUP: 2 nbits + 1 with nbits the index bits (hm_lookup_batch itself takes 1..8).
  * HM_OP_SELECT has no width: both entries return 5.  hm_validate_operation itself has no width:
- * it returns HM_ERR_INVALID_ARGUMENT for HM_OP_SUB .. HM_OP_GE, HM_OP_MIN and HM_OP_MAX. */
+ * it returns HM_ERR_INVALID_ARGUMENT for HM_OP_SUB .. HM_OP_GE, HM_OP_MIN, HM_OP_MAX and
+ * HM_OP_LOOKUP. */
 hm_status hm_validate_operation_bits(const hm_ctx *ctx, hm_op op, uint32_t nbits,
                                      uint16_t *required_min_d_over_delta);
 
@@ -317,6 +324,16 @@ hm_status hm_select_out_bounds(uint32_t nbits, uint32_t cond_bound0, const uint3
  * beyond the engine's degree range HM_ERR_UNSUPPORTED. */
 hm_status hm_minmax_out_bounds(uint32_t nbits, const uint32_t *a_bound, const uint32_t *b_bound,
                                uint32_t *out_bound);
+/* Output bounds of hm_lookup_batch(a, table): they depend on the table, which is public.  With
+ * c_j the algebraic normal form of output bit j (see hm_lookup_batch), out_bound[j] = the largest
+ * sum of a_bound[i] over i in S among the sets S of c_j, and 0 when c_j is empty or holds only the
+ * empty set: the identity table gives the input's own bounds, a random byte table at one bound D
+ * gives 8 D where the top monomial is present and 7 D otherwise.  a_bound: in_bits entries; table:
+ * 2^in_bits entries of out_nbytes little-endian bytes; writes 8 out_nbytes bounds.  in_bits
+ * outside 1..8, out_nbytes outside {1, 2, 4} or a null pointer is HM_ERR_INVALID_ARGUMENT, a
+ * bound beyond the engine's degree range HM_ERR_UNSUPPORTED. */
+hm_status hm_lookup_out_bounds(uint32_t in_bits, const uint32_t *a_bound, const uint8_t *table,
+                               uint32_t out_nbytes, uint32_t *out_bound);
 /* stride (limbs per value) of a batch with these bounds */
 uint64_t hm_batch_stride(uint32_t nbits, const uint32_t *bound);
 
@@ -394,6 +411,25 @@ hm_status hm_select_batch(hm_ctx *ctx, const hm_batch *cond, const hm_batch *a, 
  * as hm_select_batch. */
 hm_status hm_minmax_batch(hm_ctx *ctx, hm_op which, const hm_batch *a, const hm_batch *b,
                           int is_signed, hm_batch *out);
+
+/* table[v] per value, for any plaintext table: v = the unsigned integer of a's low in_bits
+ * ciphertext bits (1 <= in_bits <= min(a->nbits, 8); a is read in place and its bits from in_bits
+ * up are neither read nor validated, so a Ciphered<u32>'s low nibble or a comparison's bool,
+ * in_bits = 1, can be the index), table = 2^in_bits entries of out_nbytes (1, 2 or 4)
+ * little-endian bytes in HOST memory, read during the call only (a captured graph holds no pointer
+ * to it).  With f_j(v) = bit j of table[v] and c_j its algebraic normal form,
+ * c_j[S] = XOR over S' subset of S of f_j(S') (the Moebius transform over the index bits),
+ *   out_j = sum over the S with c_j[S] = 1 of the product of a_i over i in S
+ * (the empty product is the unit polynomial; a product with a null factor is null): exact in
+ * GF(2)[X] whatever the order of evaluation.  out: out->nbits == 8 out_nbytes, out->n == a->n,
+ * bounds from hm_lookup_out_bounds over a's first in_bits bounds (larger ones are accepted,
+ * smaller ones HM_ERR_INVALID_ARGUMENT); out may not overlap a (HM_ERR_INVALID_ARGUMENT).
+ * Validates HM_OP_LOOKUP at in_bits: the requirement covers fresh index bits; an index that came
+ * out of another operation carries that operation's depth, which the caller accounts for.  One
+ * launch, no workspace; HM_ERR_UNSUPPORTED when a value does not fit a wavefront's share of
+ * LDS. */
+hm_status hm_lookup_batch(hm_ctx *ctx, const hm_batch *a, uint32_t in_bits, const uint8_t *table,
+                          uint32_t out_nbytes, hm_batch *out);
 
 /* ---------------- polynomial primitives (src/polynomial.rs), for unit parity ---------------- */
 /* Polynomial::add (polynomial.rs:190-213) per pair: out = a ^ b, exact degree. */
