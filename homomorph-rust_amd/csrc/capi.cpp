@@ -5,7 +5,8 @@
 // 310-323; Parameters::new asserts, :87-94), computes static degree bounds and the per-wave LDS
 // carve-outs of the wave-per-value circuits, and launches the kernels.  The adder's plan comes
 // from add_host.h (plan_add), the multiplier's from mul_host.cpp, the table lookup's from
-// lookup_host.h (plan_lookup).  Never throws across the ABI.
+// lookup_host.h (plan_lookup), the shifter's from shift_host.h (plan_shift).  Never throws across
+// the ABI.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,6 +22,7 @@
 #include "add_host.h"
 #include "ctx.h"
 #include "lookup_host.h"
+#include "shift_host.h"
 
 using namespace hm;
 
@@ -108,8 +110,8 @@ uint16_t min_d_over_delta(hm_op op) { // src/impls/numbers.rs:27-50
     case HM_OP_ADD: return 21;
     case HM_OP_MUL: case HM_OP_MUL_SIGNED: return 64;
     case HM_OP_SELECT: return 5; // 2m + 1 for c x_i of fresh bits, m = 2
-    default: break; // HM_OP_SUB .. HM_OP_GE, HM_OP_MIN, HM_OP_MAX, HM_OP_LOOKUP depend on the
-                    // width: borrow_min_d_over_delta
+    default: break; // HM_OP_SUB .. HM_OP_GE, HM_OP_MIN, HM_OP_MAX, HM_OP_LOOKUP and the shifts
+                    // depend on the width: borrow_min_d_over_delta
     }
     return 0xFFFF;
 }
@@ -118,14 +120,20 @@ bool is_borrow_op(hm_op op) { return op >= HM_OP_SUB && op <= HM_OP_GE; }
 bool is_compare_op(hm_op op) { return op >= HM_OP_EQ && op <= HM_OP_GE; }
 bool is_ordering_op(hm_op op) { return op >= HM_OP_LT && op <= HM_OP_GE; }
 bool is_minmax_op(hm_op op) { return op == HM_OP_MIN || op == HM_OP_MAX; }
-bool needs_width(hm_op op) { return is_borrow_op(op) || is_minmax_op(op) || op == HM_OP_LOOKUP; }
+using shift_plan::is_shift_op;
+bool needs_width(hm_op op) {
+    return is_borrow_op(op) || is_minmax_op(op) || op == HM_OP_LOOKUP || is_shift_op(op);
+}
 
 // 2m + 1 with m the borrow circuit's degree in fresh input bits: nbits + 1 for the orderings
 // (the borrow out of the top bit), nbits for subtraction and equality, nbits + 2 for min / max
 // (that borrow times x_i).  A table lookup is multilinear in its nbits index bits: m = nbits.
+// A shift or rotate of an nbits-bit value is log2 nbits selects deep: m = log2 nbits + 1 (the
+// caller has checked the width, shift_plan::stages).
 // A fresh bit's noise has degree delta + 1 <= 2 delta, so d >= (2m + 1) delta gives
 // m (delta + 1) < d.
 uint16_t borrow_min_d_over_delta(hm_op op, uint32_t nbits) {
+    if (is_shift_op(op)) return (uint16_t)(2 * shift_plan::stages(nbits) + 3);
     const uint32_t m = nbits + (is_ordering_op(op) ? 1u : is_minmax_op(op) ? 2u : 0u);
     return (uint16_t)(2 * m + 1);
 }
@@ -688,6 +696,7 @@ hm_status hm_validate_operation(const hm_ctx *c, hm_op op, uint16_t *req) try {
 hm_status hm_validate_operation_bits(const hm_ctx *c, hm_op op, uint32_t nbits, uint16_t *req) try {
     if (!needs_width(op)) return hm_validate_operation(c, op, req);
     if (!c || nbits == 0 || nbits > HM_MAX_BITS) return HM_ERR_INVALID_ARGUMENT;
+    if (is_shift_op(op) && !shift_plan::stages(nbits)) return HM_ERR_INVALID_ARGUMENT;
     const uint16_t m = borrow_min_d_over_delta(op, nbits);
     if (req) *req = m;
     if ((uint32_t)c->d < (uint32_t)m * (uint32_t)c->delta) return HM_ERR_INVALID_PARAMETERS;
@@ -787,6 +796,14 @@ hm_status hm_lookup_out_bounds(uint32_t in_bits, const uint32_t *a, const uint8_
     uint32_t coef[kLookupMaxOut][8];
     lookup_plan::moebius(in_bits, table, out_nbytes, coef);
     return lookup_plan::bounds(in_bits, a, coef, 8 * out_nbytes, out);
+} HM_ABI_CATCH
+
+// Degree bounds of a shift or rotate by an encrypted amount.
+hm_status hm_shift_out_bounds(hm_op which, uint32_t nbits, const uint32_t *a, const uint32_t *s,
+                              uint32_t *out) try {
+    if (!a || !s || !out || !is_shift_op(which) || !shift_plan::stages(nbits))
+        return HM_ERR_INVALID_ARGUMENT;
+    return shift_plan::bounds(which, nbits, a, s, out);
 } HM_ABI_CATCH
 
 hm_status hm_minmax_out_bounds(uint32_t L, const uint32_t *a, const uint32_t *b,
@@ -1140,6 +1157,34 @@ hm_status hm_lookup_batch(hm_ctx *c, const hm_batch *a, uint32_t in_bits, const 
     for (uint32_t j = 0; j < out->nbits; ++j) G.ob[j] = out->bound[j];
     DeviceGuard g(c->device);
     return launch_lookup(G, c->stream) ? hip_fail(c, hipGetLastError()) : HM_OK;
+} HM_ABI_CATCH
+
+hm_status hm_shift_batch(hm_ctx *c, hm_op which, const hm_batch *a, const hm_batch *amount,
+                         int is_signed, hm_batch *out) try {
+    if (!c || !a || !amount || !out || !is_shift_op(which)) return HM_ERR_INVALID_ARGUMENT;
+    if (hm_status st = check_batch(a); st) return st;
+    if (hm_status st = check_batch(amount); st) return st;
+    if (hm_status st = check_batch(out); st) return st;
+    const uint32_t L = shift_plan::stages(a->nbits);
+    if (!L || amount->nbits < L || out->nbits != a->nbits || amount->n != a->n || out->n != a->n)
+        return HM_ERR_INVALID_ARGUMENT;
+    if (hm_status st = hm_validate_operation_bits(c, which, a->nbits, nullptr); st) return st;
+    std::vector<uint32_t> need(a->nbits);
+    if (hm_status st = shift_plan::bounds(which, a->nbits, a->bound, amount->bound, need.data()); st)
+        return st;
+    if (!covers(out, need) || overlaps(out, a) || overlaps(out, amount))
+        return HM_ERR_INVALID_ARGUMENT;
+    if (a->n == 0) return HM_OK;
+    ShiftArgs G{};
+    if (hm_status st = plan_shift(shift_plan::mode_of(which, is_signed != 0), a->nbits, a->bound,
+                                  amount->bound, need.data(), G);
+        st)
+        return st;
+    G.a = batch_arg(a), G.s = batch_arg(amount), G.out = batch_arg(out);
+    G.n = a->n, G.status = c->d_status;
+    fill_bounds(G.ob, out);
+    DeviceGuard g(c->device);
+    return launch_shift(G, c->stream) ? hip_fail(c, hipGetLastError()) : HM_OK;
 } HM_ABI_CATCH
 
 // ------------------------------------------------------------------ polynomial primitives

@@ -199,6 +199,49 @@ struct LookupArgs {
     int *status;
 };
 
+// Shift or rotate by an encrypted amount (kernels.hip shift_kernel): a barrel
+// shifter of L = log2 nbits stages, one per amount bit s_t, step k = 2^t,
+//   y_i = x_i + s_t (x_i + x_src(i)),      src = shift_src(mode, nbits, k, i),
+// one wavefront per value.  The whole value lives in the wave's LDS slice across the stages, IN
+// PLACE, one slot per bit sized by its output bound.  The stages run from the widest step down
+// (they commute); a stage walks the bits away from its sources (from the top bit down when
+// src < i: SHL, ROTL; from bit 0 up otherwise), so a source is read before its slot is rewritten;
+// a rotate first saves the k bits that wrap around (k slots at that stage's input bound: small,
+// because the wide steps come first).  Each product is formed in a one-bit buffer and copied to
+// its slot; the last stage whose s_t is not null sends its products to the output instead.  A
+// null s_t leaves the value where it is.  Everything below but the batches, n and status is
+// filled by shift_host.h plan_shift.  The bounds and the slot offsets travel by value: every
+// index into them is wave-uniform (dev_common.h).
+enum { kShiftShl = 0, kShiftShr = 1, kShiftSar = 2, kShiftRotl = 3, kShiftRotr = 4 };
+constexpr uint32_t kShiftMaxStages = 7; // log2 HM_MAX_BITS
+// The bit a stage of step k mixes into bit i of an nbits-bit value; -1: the null polynomial.
+__attribute__((always_inline)) constexpr int32_t shift_src(uint32_t mode, uint32_t nbits, uint32_t k, uint32_t i) {
+    switch (mode) {
+    case kShiftShl: return i >= k ? (int32_t)(i - k) : -1;
+    case kShiftShr: return i + k < nbits ? (int32_t)(i + k) : -1;
+    case kShiftSar: return i + k < nbits ? (int32_t)(i + k) : (int32_t)(nbits - 1);
+    case kShiftRotl: return (int32_t)((i + nbits - k) & (nbits - 1));
+    default: return (int32_t)((i + k) & (nbits - 1)); // kShiftRotr
+    }
+}
+struct ShiftArgs {
+    BatchArg a, s, out; // s: the amount, read in place (its low L bits)
+    uint64_t n;
+    uint32_t mode;      // kShiftShl .. kShiftRotr
+    uint32_t nbits, L;  // a power of two in 2..128 and its log2
+    // word offsets in a wave's LDS slice: word counts (nbits of the value's bits, 8 of the amount
+    // bits, nbits / 2 of the saved bits) | the amount bits at soff[t] | x_i + x_src | the one-bit
+    // product buffer | the saved bits of a rotate's stage t, sv[t] words each, at oS | the value
+    // at oV, bit i at off[i], cV words in all
+    uint32_t lds_per_wave, oN, oX, oT, oS, oV, cV;
+    uint32_t sv[kShiftMaxStages];
+    uint32_t soff[kShiftMaxStages];
+    uint32_t off[HM_MAX_BITS];
+    uint32_t sb[kShiftMaxStages];
+    int *status;
+    Bounds ab, ob;
+};
+
 // Column-parallel carry-save multiplier (mul_engine.hip, mul_host.cpp).  Column i of
 // mul_unsigned_internal (common.rs:66-105) XORs its items x_0..x_{n-1} (the partial products
 // a_j b_{i-j}, then the previous column's carries) into result_i and pushes the carry
@@ -482,6 +525,7 @@ int launch_borrow(const BorrowArgs &a, void *stream);
 int launch_minmax(const MinMaxArgs &a, void *stream);
 int launch_select(const SelectArgs &a, void *stream);
 int launch_lookup(const LookupArgs &a, void *stream);
+int launch_shift(const ShiftArgs &a, void *stream);
 int launch_mul_stage(const MulStageArgs &a, void *stream);
 int launch_mul_pp(const MulPPArgs &a, void *stream);
 int launch_mul_scan(const MulScanArgs &a, void *stream);

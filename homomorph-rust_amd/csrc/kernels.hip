@@ -6,6 +6,7 @@
 //                   borrow times a_i + b_i, in one launch (s4.4b)
 //   select_kernel   cond ? a : b on an encrypted bool (s4.4b)
 //   lookup_kernel   T[v] for a plaintext table T and an encrypted index of up to 8 bits (s4.4c)
+//   shift_kernel    <<, >>, rotates by an encrypted amount: a barrel shifter in LDS (s4.4d)
 //   poly_* kernels single-polynomial primitives for unit parity (polynomial.rs:190-365)
 // (adder: adder.hip; cipher: cipher.hip; carry-save multiplier: mul_engine.hip)
 #include <hip/hip_runtime.h>
@@ -14,8 +15,8 @@
 
 namespace hm {
 
-// The launch of the wave-per-value circuits (gates, borrow chain, min / max, select, lookup): one
-// wavefront per value, 4 per block, lds_per_wave words of dynamic LDS each.
+// The launch of the wave-per-value circuits (gates, borrow chain, min / max, select, lookup,
+// shift): one wavefront per value, 4 per block, lds_per_wave words of dynamic LDS each.
 template <class Args>
 static int launch_wave_per_value(void (*kernel)(Args), const Args &g, uint32_t lds_per_wave,
                                  void *stream) {
@@ -361,6 +362,115 @@ __global__ void __launch_bounds__(256) lookup_kernel(LookupArgs G) {
 
 int launch_lookup(const LookupArgs &g, void *stream) {
     return launch_wave_per_value(lookup_kernel, g, g.lds_per_wave, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Shift or rotate by an encrypted amount (ShiftArgs): L stages
+// y_i = x_i + s_t (x_i + x_src(i)) over a value that stays in LDS, in place.  The stages run from
+// the widest step down; a stage walks the bits away from its sources and a rotate saves the bits
+// that wrap around first, so every source is read before its slot is rewritten.  Each product is
+// formed in T (wave_mul's Dst may not alias U or Add) and copied to its slot; the last stage whose
+// s_t is not null stores its products to the output instead and rewrites nothing.  s_t, the short
+// operand, is the uniform one.  A null s_t is skipped: its stage is the identity.
+
+// Dst[0..n) = Src[0..n)
+__device__ __forceinline__ void wave_copy(const uint32_t *Src, int n, uint32_t *Dst) {
+    for (int w = lane_id(); w < n; w += kWave) Dst[w] = Src[w];
+}
+
+__global__ void __launch_bounds__(256) shift_kernel(ShiftArgs G) {
+    extern __shared__ uint32_t lds[];
+    const int wave = (int)rfl(threadIdx.x >> 6); // wave-uniform by construction
+    const uint64_t e = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave;
+    if (e >= G.n) return;
+    const int lane = lane_id();
+    uint32_t *L = lds + (size_t)wave * G.lds_per_wave;
+    uint32_t *NB = L + G.oN, *NS = NB + G.nbits, *NV = NS + 8; // word counts: value, amount, saved
+    uint32_t *X = L + G.oX, *T = L + G.oT, *Sv = L + G.oS, *B = L + G.oV;
+    // every bit of a into its slot, the low L bits of the amount into theirs
+    const uint64_t *pa = G.a.limbs + e * G.a.stride;
+    uint32_t offa = 0;
+    for (uint32_t i = 0; i < G.nbits; ++i) {
+        const int na = load_bit(pa + offa, rfl(G.a.degree[e * G.a.dstride + i]), G.ab.b[i],
+                                B + G.off[i], G.status);
+        if (lane == 0) NB[i] = (uint32_t)na;
+        offa += cap_of(G.ab.b[i]);
+    }
+    const uint64_t *ps = G.s.limbs + e * G.s.stride;
+    uint32_t offs = 0;
+    int last = -1; // the last stage to run that is not the identity: the lowest such t
+    for (uint32_t t = 0; t < G.L; ++t) {
+        const int ns = load_bit(ps + offs, rfl(G.s.degree[e * G.s.dstride + t]), G.sb[t],
+                                L + G.soff[t], G.status);
+        if (lane == 0) NS[t] = (uint32_t)ns;
+        if (ns && last < 0) last = (int)t;
+        offs += cap_of(G.sb[t]);
+    }
+    wsync();
+    uint64_t *po = G.out.limbs + e * G.out.stride;
+    uint32_t *od = G.out.degree + e * G.nbits;
+    if (last < 0) { // the amount is the null value: out = a
+        uint32_t offo = 0;
+        for (uint32_t i = 0; i < G.nbits; ++i) {
+            store_xor_bit(B + G.off[i], (int)rfl(NB[i]), nullptr, 0, po + offo, G.ob.b[i], od + i,
+                          G.status);
+            offo += cap_of(G.ob.b[i]);
+        }
+        return;
+    }
+    const bool rot = G.mode == kShiftRotl || G.mode == kShiftRotr;
+    const bool down = G.mode == kShiftShl || G.mode == kShiftRotl; // src < i: from the top bit down
+    for (int t = (int)G.L - 1; t >= last; --t) {
+        const int ns = (int)rfl(NS[t]);
+        if (!ns) continue;
+        const uint32_t *S = L + G.soff[t];
+        const uint32_t k = 1u << t, sv = G.sv[t];
+        const bool fin = t == last; // nothing is rewritten: any order, nothing to save
+        if (rot && !fin) { // the k bits that wrap: the top ones (ROTL) or the low ones (ROTR)
+            for (uint32_t j = 0; j < k; ++j) {
+                const uint32_t b = down ? G.nbits - k + j : j;
+                const int nb = (int)rfl(NB[b]);
+                wave_copy(B + G.off[b], nb, Sv + j * sv);
+                if (lane == 0) NV[j] = (uint32_t)nb;
+            }
+            wsync();
+        }
+        uint32_t offo = 0;
+        for (uint32_t q = 0; q < G.nbits; ++q) {
+            const uint32_t i = down && !fin ? G.nbits - 1 - q : q;
+            uint32_t *xi = B + G.off[i];
+            const int ni = (int)rfl(NB[i]);
+            const int32_t src = (int32_t)rfl((uint32_t)shift_src(G.mode, G.nbits, k, i));
+            const uint32_t *V = xi; // src null: y_i = x_i + s_t x_i
+            int nv = ni;
+            if (src >= 0) {
+                const uint32_t *xs = B + G.off[src];
+                int nsrc = (int)rfl(NB[src]);
+                if (rot && !fin && (down ? i < k : i >= G.nbits - k)) { // src wrapped: saved
+                    const uint32_t j = down ? i : (uint32_t)src;
+                    xs = Sv + j * sv, nsrc = (int)rfl(NV[j]);
+                }
+                nv = words_of(wave_xor(xi, ni, xs, nsrc, X));
+                wsync();
+                V = X;
+            }
+            int nout;
+            const int ny = words_of(wave_mul<kQSmall, 8>(S, ns, V, nv, xi, ni, T, &nout));
+            wsync();
+            if (fin) {
+                store_xor_bit(T, ny, nullptr, 0, po + offo, G.ob.b[i], od + i, G.status);
+                offo += cap_of(G.ob.b[i]);
+            } else {
+                wave_copy(T, ny, xi);
+                if (lane == 0) NB[i] = (uint32_t)ny;
+            }
+            wsync();
+        }
+    }
+}
+
+int launch_shift(const ShiftArgs &g, void *stream) {
+    return launch_wave_per_value(shift_kernel, g, g.lds_per_wave, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

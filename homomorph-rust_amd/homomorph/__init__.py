@@ -32,11 +32,14 @@ __all__ = [
     "HomomorphicSubtraction", "HomomorphicEqual", "HomomorphicNotEqual", "HomomorphicLessThan",
     "HomomorphicLessEqual", "HomomorphicGreaterThan", "HomomorphicGreaterEqual",
     "HomomorphicSelect", "HomomorphicMin", "HomomorphicMax", "HomomorphicLookup",
+    "HomomorphicShiftLeft", "HomomorphicShiftRight", "HomomorphicRotateLeft",
+    "HomomorphicRotateRight",
     "OperationError", "ContextCryptoError", "CipherError", "EngineError", "LibraryMissing",
     "EngineGraph",
     "add_out_bounds", "mul_out_bounds", "gate_out_bounds", "sub_out_bounds",
     "compare_out_bounds", "select_out_bounds", "minmax_out_bounds", "batch_stride", "caps",
     "select_into", "minmax_into", "lookup_out_bounds", "lookup_into",
+    "shift_out_bounds", "shift_into",
 ]
 
 
@@ -189,6 +192,41 @@ class HomomorphicLookup(_WidthOp):
     requirement covers fresh index bits; an index that came out of another operation carries that
     operation's depth."""
     CODE = _lib.OP_LOOKUP
+
+
+class _ShiftOp(_WidthOp):
+    """A shift or rotate by an encrypted amount: ctx.shift(op, a, amount).  The
+    width is that of the shifted type, a power of two in 2..128; the circuit is log2(width)
+    selects deep, so m = log2(width) + 1.  The requirement covers fresh operands."""
+
+    @classmethod
+    def min_d_over_delta(cls, nbits: int) -> int:
+        nbits = int(nbits)
+        if nbits < 2 or nbits > _lib.HM_MAX_BITS or nbits & (nbits - 1):
+            raise ValueError("a shifted type has a power of two of bits in 2..128")
+        return 2 * (nbits.bit_length() - 1) + 3
+
+
+class HomomorphicShiftLeft(_ShiftOp):
+    """a << (s mod nbits), Rust's wrapping_shl."""
+    CODE = _lib.OP_SHL
+
+
+class HomomorphicShiftRight(_ShiftOp):
+    """a >> (s mod nbits), Rust's wrapping_shr: arithmetic on a signed type, logical otherwise."""
+    CODE = _lib.OP_SHR
+
+
+class HomomorphicRotateLeft(_ShiftOp):
+    CODE = _lib.OP_ROTL
+
+
+class HomomorphicRotateRight(_ShiftOp):
+    CODE = _lib.OP_ROTR
+
+
+def _is_shift(op) -> bool:
+    return isinstance(op, type) and issubclass(op, _ShiftOp)
 
 
 def _is_borrow(op) -> bool:
@@ -373,6 +411,20 @@ def lookup_out_bounds(a_bound, table, in_bits=None) -> np.ndarray:
     out = np.zeros(8 * nbytes, dtype=np.uint32)
     _check(lib().hm_lookup_out_bounds(in_bits, _p32(a), raw.ctypes.data_as(_lib.u8p), nbytes,
                                       _p32(out)), "hm_lookup_out_bounds")
+    return out
+
+
+def shift_out_bounds(op, a_bound, s_bound) -> np.ndarray:
+    """hm_shift_out_bounds: per-bit bounds of shift(op, a, amount) from a's bounds and the bounds
+    of the amount's low log2(nbits) bits (more may be given: the rest is not read)."""
+    a, s = _u32(a_bound), _u32(s_bound)
+    stages = max(int(a.size).bit_length() - 1, 0)
+    if s.size < stages:
+        raise ValueError(f"a {a.size}-bit shift reads {stages} amount bits: as many bounds")
+    s = np.ascontiguousarray(s[:stages])
+    out = np.zeros_like(a)
+    _check(lib().hm_shift_out_bounds(op.CODE, a.size, _p32(a), _p32(s), _p32(out)),
+           "hm_shift_out_bounds")
     return out
 
 
@@ -801,8 +853,8 @@ class Context:
     def validate_operation(self, op, nbits=None) -> None:
         """Context::validate_operation (src/context.rs:310-323).  Built-in operations ask the
         engine (hm_validate_operation); a user operation supplies MIN_D_OVER_DELTA itself.
-        Subtraction, the comparisons, min / max and the table lookup need a width (nbits: of the
-        type, for the lookup of the index): their requirement grows with it
+        Subtraction, the comparisons, min / max, the shifts and the table lookup need a width
+        (nbits: of the type, for the lookup of the index): their requirement grows with it
         (hm_validate_operation_bits)."""
         if not hasattr(op, "CODE"):
             req = int(op.MIN_D_OVER_DELTA)
@@ -823,6 +875,8 @@ class Context:
     def apply2(self, op, a: Ciphered, b: Ciphered, out_bound=None, signed=None) -> Ciphered:
         if _is_borrow(op):
             return self._apply_borrow(op, a, b, out_bound, signed)
+        if _is_shift(op):
+            return self.shift(op, a, b, out_bound, signed)
         self.validate_operation(op)
         if op is HomomorphicAddition:
             need = add_out_bounds(a.bound, b.bound)
@@ -892,6 +946,22 @@ class Context:
         need = lookup_out_bounds(a.bound, table, in_bits)
         out = Ciphered.empty(a.n, need if out_bound is None else out_bound, self.device, dtype)
         lookup_into(self, a, table, out, in_bits)
+        return out
+
+    def shift(self, op, a: Ciphered, amount: Ciphered, out_bound=None, signed=None) -> Ciphered:
+        """a << s, a >> s or a rotate per value by an ENCRYPTED amount (hm_shift_batch); op is
+        HomomorphicShiftLeft, HomomorphicShiftRight, HomomorphicRotateLeft or
+        HomomorphicRotateRight.  a.nbits is a power of two; the amount is any batch with at least
+        log2(a.nbits) ciphertext bits per value, of which only those low bits are read, so the
+        effective amount is s mod a.nbits.  signed (HomomorphicShiftRight only): arithmetic shift;
+        None infers it from a's plaintext dtype.  The output keeps a's plaintext dtype."""
+        if not _is_shift(op):
+            raise ValueError("shift takes one of the four shift and rotate markers")
+        self.validate_operation(op, a.nbits)
+        need = shift_out_bounds(op, a.bound, amount.bound)
+        out = Ciphered.empty(a.n, need if out_bound is None else out_bound, self.device,
+                             a.plain_dtype)
+        shift_into(self, op, a, amount, out, signed)
         return out
 
     def mul_plan_work(self, a_bound, b_bound, k=None, signed=False) -> float:
@@ -1036,6 +1106,17 @@ def lookup_into(ctx: Context, a: Ciphered, table, out: Ciphered, in_bits=None) -
     ctx._launch(lambda: lib().hm_lookup_batch(ctx._h, ctypes.byref(ca), in_bits,
                                               raw.ctypes.data_as(_lib.u8p), nbytes,
                                               ctypes.byref(co)), "hm_lookup_batch")
+
+
+def shift_into(ctx: Context, op, a: Ciphered, amount: Ciphered, out: Ciphered, signed=None) -> None:
+    """hm_shift_batch into a preallocated output (bounds: shift_out_bounds).  signed defaults from
+    a's plaintext dtype, as for comparisons; only HomomorphicShiftRight looks at it."""
+    if signed is None:
+        signed = a.plain_dtype is not None and np.issubdtype(a.plain_dtype, np.signedinteger)
+    ca, cs, co = a._c(), amount._c(), out._c()
+    ctx._launch(lambda: lib().hm_shift_batch(ctx._h, op.CODE, ctypes.byref(ca), ctypes.byref(cs),
+                                             int(bool(signed)), ctypes.byref(co)),
+                "hm_shift_batch")
 
 
 def minmax_into(ctx: Context, op, a: Ciphered, b: Ciphered, out: Ciphered, signed=None) -> None:

@@ -36,6 +36,7 @@ OP_AND, OP_OR, OP_XOR, OP_NOT, OP_ADD, OP_MUL, OP_MUL_SIGNED = range(7)
 OP_SUB, OP_EQ, OP_NE, OP_LT, OP_LE, OP_GT, OP_GE = range(7, 14)
 OP_SELECT, OP_MIN, OP_MAX = range(14, 17)
 OP_LOOKUP = 17
+OP_SHL, OP_SHR, OP_ROTL, OP_ROTR = range(18, 22)
 
 u64p = ctypes.POINTER(ctypes.c_uint64)
 u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -117,6 +118,10 @@ SIGNATURES = {
     "hm_lookup_out_bounds": (ctypes.c_int, [ctypes.c_uint32, u32p, u8p, ctypes.c_uint32, u32p]),
     "hm_lookup_batch": (ctypes.c_int, [vp, ctypes.POINTER(HmBatch), ctypes.c_uint32, u8p,
                                        ctypes.c_uint32, ctypes.POINTER(HmBatch)]),
+    "hm_shift_out_bounds": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, u32p, u32p, u32p]),
+    "hm_shift_batch": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(HmBatch),
+                                      ctypes.POINTER(HmBatch), ctypes.c_int,
+                                      ctypes.POINTER(HmBatch)]),
     "hm_poly_add_batch": (ctypes.c_int, [vp] + [ctypes.POINTER(HmPolys)] * 3),
     "hm_poly_mul_batch": (ctypes.c_int, [vp] + [ctypes.POINTER(HmPolys)] * 3),
     "hm_poly_rem_batch": (ctypes.c_int, [vp, ctypes.POINTER(HmPolys), u64p, ctypes.c_size_t,

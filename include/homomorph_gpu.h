@@ -34,13 +34,14 @@
 extern "C" {
 #endif
 
-#define HM_ABI_VERSION 8 /* 4: kernel timing by device stamps (HM_TIME_*), hm_ctx_last_hip_error;
+#define HM_ABI_VERSION 9 /* 4: kernel timing by device stamps (HM_TIME_*), hm_ctx_last_hip_error;
                             5: hm_ctx_clear_kernel_timing, hm_ctx_set_mul_scratch;
                             6: HM_OP_SUB .. HM_OP_GE, hm_sub_batch, hm_compare_batch, their bounds,
                                hm_validate_operation_bits;
                             7: HM_OP_SELECT, HM_OP_MIN, HM_OP_MAX, hm_select_batch,
                                hm_minmax_batch, their bounds;
-                            8: HM_OP_LOOKUP, hm_lookup_batch, hm_lookup_out_bounds */
+                            8: HM_OP_LOOKUP, hm_lookup_batch, hm_lookup_out_bounds;
+                            9: HM_OP_SHL .. HM_OP_ROTR, hm_shift_batch, hm_shift_out_bounds */
 #define HM_MAX_BITS 128 /* u128 is the widest type with impls (src/impls/numbers/uint.rs:58) */
 
 typedef enum hm_status {
@@ -108,6 +109,15 @@ typedef enum hm_op {
      * a multilinear polynomial of degree at most n in those bits, so m = n and min d/delta 2n + 1
      * (a byte 17, a bool 3): width dependent (hm_validate_operation_bits), for fresh index bits. */
     HM_OP_LOOKUP = 17,        /* HomomorphicLookup           table[a] */
+    /* Shifts and rotates of an n-bit value, n a power of two in 2..128, by an ENCRYPTED amount
+     * (hm_shift_batch): a barrel shifter of log2 n stages, each a select between the value and its
+     * copy moved by 2^t on amount bit t, so m = log2 n + 1 and min d/delta 2 log2 n + 3 (u8 9,
+     * u16 11, u32 13, u64 15, u128 17): width dependent (hm_validate_operation_bits), for fresh
+     * operands.  (A shift by a plaintext amount only renumbers ciphertext bits: no kernel.) */
+    HM_OP_SHL = 18,           /* HomomorphicShiftLeft        a << (s mod n) */
+    HM_OP_SHR = 19,           /* HomomorphicShiftRight       a >> (s mod n), logical or arithmetic */
+    HM_OP_ROTL = 20,          /* HomomorphicRotateLeft       a.rotate_left(s mod n) */
+    HM_OP_ROTR = 21,          /* HomomorphicRotateRight      a.rotate_right(s mod n) */
 } hm_op;
 
 typedef struct hm_ctx hm_ctx;
@@ -262,9 +272,11 @@ hm_status hm_validate_operation(const hm_ctx *ctx, hm_op op, uint16_t *required_
  * so results on fresh inputs decrypt exactly; nbits outside 1..HM_MAX_BITS is
  * HM_ERR_INVALID_ARGUMENT.  HM_OP_MIN / HM_OP_MAX likewise: 2 nbits + 5 (u32: 69).
  * HM_OP_LOOKUP: 2 nbits + 1 with nbits the index bits (hm_lookup_batch itself takes 1..8).
+ * HM_OP_SHL .. HM_OP_ROTR: 2 log2(nbits) + 3 with nbits the width of the shifted type (u32: 13);
+ * a width that is not a power of two in 2..HM_MAX_BITS is HM_ERR_INVALID_ARGUMENT.
  * HM_OP_SELECT has no width: both entries return 5.  hm_validate_operation itself has no width:
- * it returns HM_ERR_INVALID_ARGUMENT for HM_OP_SUB .. HM_OP_GE, HM_OP_MIN, HM_OP_MAX and
- * HM_OP_LOOKUP. */
+ * it returns HM_ERR_INVALID_ARGUMENT for HM_OP_SUB .. HM_OP_GE, HM_OP_MIN, HM_OP_MAX,
+ * HM_OP_LOOKUP and HM_OP_SHL .. HM_OP_ROTR. */
 hm_status hm_validate_operation_bits(const hm_ctx *ctx, hm_op op, uint32_t nbits,
                                      uint16_t *required_min_d_over_delta);
 
@@ -334,6 +346,16 @@ hm_status hm_minmax_out_bounds(uint32_t nbits, const uint32_t *a_bound, const ui
  * bound beyond the engine's degree range HM_ERR_UNSUPPORTED. */
 hm_status hm_lookup_out_bounds(uint32_t in_bits, const uint32_t *a_bound, const uint8_t *table,
                                uint32_t out_nbytes, uint32_t *out_bound);
+/* Output bounds of hm_shift_batch(which, a, amount), which = HM_OP_SHL .. HM_OP_ROTR (anything
+ * else is HM_ERR_INVALID_ARGUMENT) on nbits-bit values, nbits a power of two in 2..128 (anything
+ * else is HM_ERR_INVALID_ARGUMENT, as is a null pointer).  a_bound: nbits entries; s_bound: the
+ * log2(nbits) bounds of the amount's low bits.  With S the sum of s_bound, out_bound[j] = S + the
+ * widest a_bound[i] among the bits that can reach bit j: i <= j for HM_OP_SHL, i >= j for
+ * HM_OP_SHR (logical and arithmetic alike), every i for the rotates.  (u32 at d + dp = 256, a u8
+ * or u32 amount: every bit 1536, 800 limbs per value.)  A bound beyond the engine's degree range
+ * is HM_ERR_UNSUPPORTED. */
+hm_status hm_shift_out_bounds(hm_op which, uint32_t nbits, const uint32_t *a_bound,
+                              const uint32_t *s_bound, uint32_t *out_bound);
 /* stride (limbs per value) of a batch with these bounds */
 uint64_t hm_batch_stride(uint32_t nbits, const uint32_t *bound);
 
@@ -430,6 +452,30 @@ hm_status hm_minmax_batch(hm_ctx *ctx, hm_op which, const hm_batch *a, const hm_
  * LDS. */
 hm_status hm_lookup_batch(hm_ctx *ctx, const hm_batch *a, uint32_t in_bits, const uint8_t *table,
                           uint32_t out_nbytes, hm_batch *out);
+
+/* a << s, a >> s, a.rotate_left(s) or a.rotate_right(s) per value for an ENCRYPTED amount s,
+ * which = HM_OP_SHL, HM_OP_SHR, HM_OP_ROTL or HM_OP_ROTR (anything else is
+ * HM_ERR_INVALID_ARGUMENT); is_signed matters for HM_OP_SHR only and makes it arithmetic (the
+ * vacated bits take the sign bit's polynomial).  n = a->nbits is a power of two in 2..128 and
+ * L = log2 n; the effective amount is s mod n, Rust's wrapping_shl / wrapping_shr / rotate_*:
+ * amount is read in place and only its low L ciphertext bits are read and validated
+ * (amount->nbits >= L), so a Ciphered<u8> or a Ciphered<u32> can shift a u32.  One stage per
+ * amount bit s_t, with step k = 2^t:
+ *   y_i = x_i + s_t (x_i + x_src(i)),   src(i) = i - k (SHL), i + k (SHR), (i -+ k) mod n (ROTL,
+ *   ROTR); a src outside 0..n-1 is the null polynomial, or x_{n-1} for the arithmetic SHR.
+ * The stages are commuting linear maps of the value, so the result is one polynomial whatever
+ * order they run in: exact in GF(2)[X].  A null s_t leaves the value unchanged, the unit
+ * polynomial moves it by k.  out: out->nbits == a->nbits, amount->n == a->n == out->n, bounds from
+ * hm_shift_out_bounds over the amount's first L bounds (larger ones are accepted, smaller ones
+ * HM_ERR_INVALID_ARGUMENT); out may not overlap a or amount, in limbs or in degree words
+ * (HM_ERR_INVALID_ARGUMENT).  Validates which at a->nbits: the requirement covers fresh operands;
+ * operands that came out of another operation carry that operation's depth, which the caller
+ * accounts for.  One launch, no workspace: the value stays in LDS across the stages, in place;
+ * HM_ERR_UNSUPPORTED (before any launch) when a value does not fit a wavefront's share of LDS
+ * (the value at its output bounds, about 1/16 of 160 KiB: every width up to u128 at
+ * d + dp = 256, u64 at 512 and u32 at 1024 fit, u128 at d + dp = 512 does not). */
+hm_status hm_shift_batch(hm_ctx *ctx, hm_op which, const hm_batch *a, const hm_batch *amount,
+                         int is_signed, hm_batch *out);
 
 /* ---------------- polynomial primitives (src/polynomial.rs), for unit parity ---------------- */
 /* Polynomial::add (polynomial.rs:190-213) per pair: out = a ^ b, exact degree. */
