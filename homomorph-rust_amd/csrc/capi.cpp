@@ -2,11 +2,11 @@
 //
 // Owns the per-device context (keys, derived decrypt table, workspace, stream), validates every
 // call the way the reference's safe wrappers do (Context::validate_operation, src/context.rs:
-// 310-323; Parameters::new asserts, :87-94), computes static degree bounds and the per-wave LDS
-// carve-outs of the wave-per-value circuits, and launches the kernels.  The adder's plan comes
-// from add_host.h (plan_add), the multiplier's from mul_host.cpp, the table lookup's from
-// lookup_host.h (plan_lookup), the shifter's from shift_host.h (plan_shift).  Never throws across
-// the ABI.
+// 310-323; Parameters::new asserts, :87-94) and launches the kernels.  The static degree bounds
+// and the plans come from host-only headers: the adder's from add_host.h (plan_add), the
+// wave-per-value circuits' from circuit_host.h (plan_gate, plan_borrow, plan_select),
+// lookup_host.h (plan_lookup) and shift_host.h (plan_shift); the multiplier's from mul_host.cpp.
+// Never throws across the ABI.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,6 +20,7 @@
 #include <sys/random.h>
 
 #include "add_host.h"
+#include "circuit_host.h"
 #include "ctx.h"
 #include "lookup_host.h"
 #include "shift_host.h"
@@ -138,17 +139,6 @@ uint16_t borrow_min_d_over_delta(hm_op op, uint32_t nbits) {
     return (uint16_t)(2 * m + 1);
 }
 
-// Borrow bounds wb_0 = 0, wb_{i+1} = max(a_i + b_i, max(a_i, b_i) + wb_i) for i < upto; false
-// beyond the engine's degree range.  wb[i] for i <= upto.
-bool borrow_bounds(uint32_t upto, const uint32_t *a, const uint32_t *b, std::vector<int64_t> &wb) {
-    wb.assign(upto + 1, 0);
-    for (uint32_t i = 0; i < upto; ++i) {
-        wb[i + 1] = std::max<int64_t>((int64_t)a[i] + b[i], std::max<int64_t>(a[i], b[i]) + wb[i]);
-        if (wb[i + 1] >= (int64_t)1 << 30) return false;
-    }
-    return true;
-}
-
 // the bound of an output must cover the computed bound, bit by bit
 bool covers(const hm_batch *out, const std::vector<uint32_t> &need) {
     for (uint32_t i = 0; i < out->nbits; ++i)
@@ -178,49 +168,18 @@ hm_status check_operands(std::initializer_list<Operand> ops) {
     return HM_OK;
 }
 
-// LDS words of the operand rows of the wave-per-value circuits: two words per limb of the widest
-// bit of a, of b (null: a unary gate, two words) and of either
-struct Slots {
-    uint32_t SA = 2, SB = 2, SX = 2;
-};
-Slots operand_slots(const hm_batch *a, const hm_batch *b) {
-    Slots s;
-    for (uint32_t i = 0; i < a->nbits; ++i) {
-        s.SA = std::max(s.SA, 2 * cap_of(a->bound[i]));
-        if (b) s.SB = std::max(s.SB, 2 * cap_of(b->bound[i]));
-    }
-    s.SX = std::max(s.SA, s.SB);
-    return s;
+// The operands, counts, bounds and status word of a wave-per-value circuit (b null: a unary gate)
+void fill_io(CircuitIO &io, hm_ctx *c, const hm_batch *a, const hm_batch *b, const hm_batch *out) {
+    io.a = batch_arg(a), io.out = batch_arg(out);
+    io.n = a->n, io.nbits = a->nbits;
+    io.status = c->d_status;
+    fill_bounds(io.ab, a), fill_bounds(io.ob, out);
+    if (b) io.b = batch_arg(b), fill_bounds(io.bb, b);
 }
 
-// The ripple-borrow chain's slice, chain = the degree bound of the last borrow (or equality
-// prefix) formed: a_i | b_i | x_i | p_i | generate term a_i b_i + b_i | two borrow buffers: the
-// widest product p_i w_i spans words(p_i) + words(w_i) <= SX + chain / 32 + 1 words
-BorrowLayout borrow_layout(const Slots &s, int64_t chain) {
-    BorrowLayout y{};
-    y.oA = 0, y.oB = s.SA + 2, y.oX = y.oB + s.SB + 2, y.oP = y.oX + s.SX + 2, y.oG = y.oP + s.SX + 2;
-    y.oW = y.oG + s.SA + s.SB + 2;
-    y.cw = s.SX + (uint32_t)(chain / 32) + 3;
-    y.lds_per_wave = y.oW + 2 * y.cw;
-    return y;
-}
-
-// The operands, counts, bounds and status word of an argument block (b null: a unary gate)
+// Launches a planned wave-per-value circuit over checked batches
 template <class Args>
-void fill_io(Args &G, hm_ctx *c, const hm_batch *a, const hm_batch *b, const hm_batch *out) {
-    G.a = batch_arg(a), G.out = batch_arg(out);
-    G.n = a->n, G.nbits = a->nbits;
-    G.status = c->d_status;
-    fill_bounds(G.ab, a), fill_bounds(G.ob, out);
-    if (b) G.b = batch_arg(b), fill_bounds(G.bb, b);
-}
-
-// Launches a wave-per-value circuit over checked batches: four waves' LDS slices within a CU
-template <class Args>
-hm_status run_circuit(hm_ctx *c, Args &G, uint32_t lds_per_wave, const hm_batch *a,
-                      const hm_batch *b, const hm_batch *out, int (*launch)(const Args &, void *)) {
-    if ((size_t)lds_per_wave * 16 > 160 * 1024) return HM_ERR_UNSUPPORTED;
-    fill_io(G, c, a, b, out);
+hm_status run_circuit(hm_ctx *c, const Args &G, int (*launch)(const Args &, void *)) {
     DeviceGuard g(c->device);
     return launch(G, c->stream) ? hip_fail(c, hipGetLastError()) : HM_OK;
 }
@@ -740,46 +699,17 @@ hm_status hm_add_out_bounds(uint32_t L, const uint32_t *a, const uint32_t *b, ui
 // Degree bounds of the ripple-borrow circuits.
 hm_status hm_sub_out_bounds(uint32_t L, const uint32_t *a, const uint32_t *b, uint32_t *out) try {
     if (!a || !b || !out || L == 0 || L > HM_MAX_BITS) return HM_ERR_INVALID_ARGUMENT;
-    std::vector<int64_t> wb;
-    if (!borrow_bounds(L - 1, a, b, wb)) return HM_ERR_UNSUPPORTED;
-    for (uint32_t i = 0; i < L; ++i) {
-        const int64_t s = std::max<int64_t>(std::max(a[i], b[i]), wb[i]);
-        if (s >= (int64_t)1 << 30) return HM_ERR_UNSUPPORTED;
-        out[i] = (uint32_t)s;
-    }
-    return HM_OK;
+    return sub_bounds(L, a, b, out);
 } HM_ABI_CATCH
 
 hm_status hm_compare_out_bounds(hm_op cmp, uint32_t L, const uint32_t *a, const uint32_t *b,
                                 uint32_t out[8]) try {
     if (!a || !b || !out || L == 0 || L > HM_MAX_BITS || !is_compare_op(cmp))
         return HM_ERR_INVALID_ARGUMENT;
-    int64_t r = 0;
-    if (is_ordering_op(cmp)) { // (the recurrence is symmetric: exchanging the operands keeps it)
-        std::vector<int64_t> wb;
-        if (!borrow_bounds(L, a, b, wb)) return HM_ERR_UNSUPPORTED;
-        r = wb[L];
-    } else {
-        for (uint32_t i = 0; i < L; ++i) r += std::max(a[i], b[i]);
-        if (r >= (int64_t)1 << 30) return HM_ERR_UNSUPPORTED;
-    }
-    out[0] = (uint32_t)r;
-    for (int k = 1; k < 8; ++k) out[k] = 0;
-    return HM_OK;
+    return compare_bounds(is_ordering_op(cmp), L, a, b, out);
 } HM_ABI_CATCH
 
-// Degree bounds of select, min and max: the condition's bound (for min / max
-// the last borrow's, wb_nbits) plus the wider operand's, bit by bit.
-static hm_status choice_bounds(uint32_t L, int64_t cond, const uint32_t *a, const uint32_t *b,
-                               uint32_t *out) {
-    for (uint32_t i = 0; i < L; ++i) {
-        const int64_t s = cond + std::max(a[i], b[i]);
-        if (s >= (int64_t)1 << 30) return HM_ERR_UNSUPPORTED;
-        out[i] = (uint32_t)s;
-    }
-    return HM_OK;
-}
-
+// Degree bounds of select, min and max.
 hm_status hm_select_out_bounds(uint32_t L, uint32_t cond_bound0, const uint32_t *a,
                                const uint32_t *b, uint32_t *out) try {
     if (!a || !b || !out || L == 0 || L > HM_MAX_BITS) return HM_ERR_INVALID_ARGUMENT;
@@ -809,9 +739,7 @@ hm_status hm_shift_out_bounds(hm_op which, uint32_t nbits, const uint32_t *a, co
 hm_status hm_minmax_out_bounds(uint32_t L, const uint32_t *a, const uint32_t *b,
                                uint32_t *out) try {
     if (!a || !b || !out || L == 0 || L > HM_MAX_BITS) return HM_ERR_INVALID_ARGUMENT;
-    std::vector<int64_t> wb;
-    if (!borrow_bounds(L, a, b, wb)) return HM_ERR_UNSUPPORTED;
-    return choice_bounds(L, wb[L], a, b, out);
+    return minmax_bounds(L, a, b, out);
 } HM_ABI_CATCH
 
 hm_status hm_mul_out_bounds(uint32_t L, const uint32_t *a, const uint32_t *b, int is_signed,
@@ -846,18 +774,7 @@ hm_status hm_gate_out_bounds(hm_op g, uint32_t L, const uint32_t *a, const uint3
                              uint32_t *out) try {
     if (!a || !out || L == 0 || L > HM_MAX_BITS) return HM_ERR_INVALID_ARGUMENT;
     if (g != HM_OP_NOT && !b) return HM_ERR_INVALID_ARGUMENT;
-    for (uint32_t i = 0; i < L; ++i) {
-        uint64_t v;
-        switch (g) {
-        case HM_OP_AND: case HM_OP_OR: v = (uint64_t)a[i] + b[i]; break;
-        case HM_OP_XOR: v = std::max(a[i], b[i]); break;
-        case HM_OP_NOT: v = a[i]; break;
-        default: return HM_ERR_INVALID_ARGUMENT;
-        }
-        if (v >= (1u << 30)) return HM_ERR_UNSUPPORTED;
-        out[i] = (uint32_t)v;
-    }
-    return HM_OK;
+    return gate_bounds(g, L, a, b, out);
 } HM_ABI_CATCH
 
 // ------------------------------------------------------------------ cipher
@@ -970,7 +887,9 @@ hm_status hm_add_batch(hm_ctx *c, const hm_batch *a, const hm_batch *b, hm_batch
     DeviceGuard g(c->device);
     HM_HIP(c, grow(c, c->d_ws_add, c->ws_add_bytes, bytes));
     A.ws = c->d_ws_add;
-    fill_io(A, c, a, b, out);
+    A.a = batch_arg(a), A.b = batch_arg(b), A.out = batch_arg(out);
+    A.n = a->n, A.nbits = L, A.status = c->d_status;
+    fill_bounds(A.ab, a), fill_bounds(A.bb, b), fill_bounds(A.ob, out);
     A.kt = c->ktimer(HM_TIME_ADD_CHAIN);
     // Two-stage pipeline (not while timing the chain): the batch in two halves, the second
     // half's prep on the auxiliary stream right after the first half's, so it runs beside the
@@ -1031,12 +950,11 @@ hm_status hm_gate_batch(hm_ctx *c, hm_op gate, const hm_batch *a, const hm_batch
         return st;
     if (!covers(out, need)) return HM_ERR_INVALID_ARGUMENT;
     if (a->n == 0) return HM_OK;
-    const Slots s = operand_slots(a, b);
     GateArgs G{};
     G.op = gate;
-    G.oA = 0, G.oB = s.SA + 2, G.oT = G.oB + s.SB + 2;
-    G.lds_per_wave = G.oT + 2 * (s.SA + s.SB) + 8;
-    return run_circuit(c, G, G.lds_per_wave, a, b, out, launch_gate);
+    if (hm_status st = plan_gate(L, a->bound, b ? b->bound : nullptr, G); st) return st;
+    fill_io(G.io, c, a, b, out);
+    return run_circuit(c, G, launch_gate);
 } HM_ABI_CATCH
 
 // The ripple-borrow kernel over checked batches (a, b: L bits; out covers its bounds).  chain: the
@@ -1045,8 +963,9 @@ static hm_status borrow_run(hm_ctx *c, int mode, bool flip, bool sgn, const hm_b
                             const hm_batch *b, hm_batch *out, int64_t chain) {
     BorrowArgs G{};
     G.mode = mode, G.flip = flip, G.sgn = sgn;
-    G.lay = borrow_layout(operand_slots(a, b), chain);
-    return run_circuit(c, G, G.lay.lds_per_wave, a, b, out, launch_borrow);
+    if (hm_status st = plan_borrow(a->nbits, a->bound, b->bound, chain, G.lay); st) return st;
+    fill_io(G.io, c, a, b, out);
+    return run_circuit(c, G, launch_borrow);
 }
 
 hm_status hm_sub_batch(hm_ctx *c, const hm_batch *a, const hm_batch *b, hm_batch *out) try {
@@ -1106,10 +1025,10 @@ hm_status hm_minmax_batch(hm_ctx *c, hm_op which, const hm_batch *a, const hm_ba
     borrow_bounds(L, a->bound, b->bound, wb);
     MinMaxArgs G{};
     G.is_max = which == HM_OP_MAX, G.sgn = is_signed != 0;
-    // borrow_run's layout with chain = wb_L: the phase-2 product x_i w_L spans
-    // words(x_i) + words(w_L) <= SX + wb_L / 32 + 1 words, like the widest p_i w_i
-    G.lay = borrow_layout(operand_slots(a, b), wb[L]);
-    return run_circuit(c, G, G.lay.lds_per_wave, a, b, out, launch_minmax);
+    // borrow_run's layout with chain = wb_L (the phase-2 product x_i w_L, circuit_host.h)
+    if (hm_status st = plan_borrow(L, a->bound, b->bound, wb[L], G.lay); st) return st;
+    fill_io(G.io, c, a, b, out);
+    return run_circuit(c, G, launch_minmax);
 } HM_ABI_CATCH
 
 hm_status hm_select_batch(hm_ctx *c, const hm_batch *cond, const hm_batch *a, const hm_batch *b,
@@ -1124,24 +1043,20 @@ hm_status hm_select_batch(hm_ctx *c, const hm_batch *cond, const hm_batch *a, co
     if (!covers(out, need) || overlaps(out, cond) || overlaps(out, a) || overlaps(out, b))
         return HM_ERR_INVALID_ARGUMENT;
     if (a->n == 0) return HM_OK;
-    const Slots s = operand_slots(a, b);
-    const uint32_t SC = 2 * cap_of(cond->bound[0]);
     SelectArgs G{};
-    // c | a_i | b_i | x_i | the product c x_i + b_i: words(c) + words(x_i) <= SC + SX words
-    G.oC = 0, G.oA = SC + 2, G.oB = G.oA + s.SA + 2, G.oX = G.oB + s.SB + 2, G.oT = G.oX + s.SX + 2;
-    G.lds_per_wave = G.oT + SC + s.SX + 2;
-    G.cond = batch_arg(cond), G.cbound = cond->bound[0];
-    return run_circuit(c, G, G.lds_per_wave, a, b, out, launch_select);
+    if (hm_status st = plan_select(L, cond->bound[0], a->bound, b->bound, G); st) return st;
+    G.cond = batch_arg(cond);
+    fill_io(G.io, c, a, b, out);
+    return run_circuit(c, G, launch_select);
 } HM_ABI_CATCH
 
 hm_status hm_lookup_batch(hm_ctx *c, const hm_batch *a, uint32_t in_bits, const uint8_t *table,
                           uint32_t out_nbytes, hm_batch *out) try {
     if (!c || !a || !table || !out) return HM_ERR_INVALID_ARGUMENT;
-    if (hm_status st = check_batch(a); st) return st;
-    if (hm_status st = check_batch(out); st) return st;
+    // (a of any width; out_nbytes = 0 asks out for a's width and is refused below)
+    if (hm_status st = check_operands({{a, 0}, {out, 8 * out_nbytes}}); st) return st;
     if (in_bits == 0 || in_bits > kLookupMaxIn || in_bits > a->nbits ||
-        (out_nbytes != 1 && out_nbytes != 2 && out_nbytes != 4) || out->nbits != 8 * out_nbytes ||
-        out->n != a->n)
+        (out_nbytes != 1 && out_nbytes != 2 && out_nbytes != 4))
         return HM_ERR_INVALID_ARGUMENT;
     if (hm_status st = hm_validate_operation_bits(c, HM_OP_LOOKUP, in_bits, nullptr); st) return st;
     LookupArgs G{};
@@ -1155,19 +1070,16 @@ hm_status hm_lookup_batch(hm_ctx *c, const hm_batch *a, uint32_t in_bits, const 
     G.a = batch_arg(a), G.out = batch_arg(out);
     G.n = a->n, G.status = c->d_status;
     for (uint32_t j = 0; j < out->nbits; ++j) G.ob[j] = out->bound[j];
-    DeviceGuard g(c->device);
-    return launch_lookup(G, c->stream) ? hip_fail(c, hipGetLastError()) : HM_OK;
+    return run_circuit(c, G, launch_lookup);
 } HM_ABI_CATCH
 
 hm_status hm_shift_batch(hm_ctx *c, hm_op which, const hm_batch *a, const hm_batch *amount,
                          int is_signed, hm_batch *out) try {
     if (!c || !a || !amount || !out || !is_shift_op(which)) return HM_ERR_INVALID_ARGUMENT;
-    if (hm_status st = check_batch(a); st) return st;
-    if (hm_status st = check_batch(amount); st) return st;
-    if (hm_status st = check_batch(out); st) return st;
+    // (the amount at its own width, of which the low L bits are read)
+    if (hm_status st = check_operands({{a, 0}, {amount, amount->nbits}, {out, 0}}); st) return st;
     const uint32_t L = shift_plan::stages(a->nbits);
-    if (!L || amount->nbits < L || out->nbits != a->nbits || amount->n != a->n || out->n != a->n)
-        return HM_ERR_INVALID_ARGUMENT;
+    if (!L || amount->nbits < L) return HM_ERR_INVALID_ARGUMENT;
     if (hm_status st = hm_validate_operation_bits(c, which, a->nbits, nullptr); st) return st;
     std::vector<uint32_t> need(a->nbits);
     if (hm_status st = shift_plan::bounds(which, a->nbits, a->bound, amount->bound, need.data()); st)
@@ -1180,11 +1092,8 @@ hm_status hm_shift_batch(hm_ctx *c, hm_op which, const hm_batch *a, const hm_bat
                                   amount->bound, need.data(), G);
         st)
         return st;
-    G.a = batch_arg(a), G.s = batch_arg(amount), G.out = batch_arg(out);
-    G.n = a->n, G.status = c->d_status;
-    fill_bounds(G.ob, out);
-    DeviceGuard g(c->device);
-    return launch_shift(G, c->stream) ? hip_fail(c, hipGetLastError()) : HM_OK;
+    fill_io(G.io, c, a, amount, out);
+    return run_circuit(c, G, launch_shift);
 } HM_ABI_CATCH
 
 // ------------------------------------------------------------------ polynomial primitives

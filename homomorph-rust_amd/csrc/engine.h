@@ -31,6 +31,11 @@ struct BatchArg {
     uint32_t dstride; // degree words per value (the batch's nbits; a low-bits view keeps it)
 };
 
+// limbs of a ciphertext bit at a degree bound (host and device)
+__attribute__((always_inline)) constexpr uint32_t cap_of(uint32_t bound) { return bound / 64 + 1; }
+// words of a polynomial at a degree bound (negative: always null; host planning)
+constexpr uint32_t words_of_bound(int64_t b) { return b < 0 ? 0u : (uint32_t)(b / 32 + 1); }
+
 // Fused adder, two launches.  add_prep_kernel (several waves per value, lanes over (bit, word))
 // validates the inputs and computes every per-bit product ab_i = a_i b_i and P_i = x_i (1 ^ ab_i)
 // into a global workspace; add_chain_kernel (one wave per value) runs the sequential carry chain.
@@ -106,15 +111,22 @@ struct DecArgs {
     KTimer kt;
 };
 
-// Gates keep their intermediates in LDS, one wavefront per value.
-struct GateArgs {
-    int op;
-    BatchArg a, b, out;
+// The wave-per-value circuits (kernels.hip: gates, borrow chain, min / max, select, lookup, shift)
+// keep their intermediates in LDS, one wavefront per value, in a slice of lds_per_wave words whose
+// layout the host plans (circuit_host.h, lookup_host.h, shift_host.h).  What their argument
+// blocks share, filled by capi.cpp fill_io: the operands, the output and their static bounds.
+struct CircuitIO {
+    BatchArg a, b, out; // b: the second operand (a shift's amount; a unary gate has none)
     uint64_t n;
-    uint32_t nbits;
-    uint32_t lds_per_wave, oA, oB, oT;
+    uint32_t nbits;     // bits of a (a comparison's output has 8, the amount its own width)
     int *status;
     Bounds ab, bb, ob;
+};
+
+struct GateArgs {
+    int op;
+    uint32_t lds_per_wave, oA, oB, oT; // circuit_host.h plan_gate
+    CircuitIO io;
 };
 
 // Ripple-borrow chain (kernels.hip borrow_kernel): subtraction, the four orderings and equality,
@@ -124,7 +136,7 @@ struct GateArgs {
 //   kBorrowLt   the same borrows through bit nbits - 1; the result is w_nbits (+ 1 when flip)
 //   kBorrowEq   e_{i+1} = p_i e_i from e_0 = 1; the result is e_nbits (+ 1 when flip)
 enum { kBorrowSub = 0, kBorrowLt = 1, kBorrowEq = 2 };
-// A wave's LDS slice on that chain, word offsets (capi.cpp borrow_layout):
+// A wave's LDS slice on that chain, word offsets (circuit_host.h plan_borrow):
 // a_i | b_i | x_i | p_i | generate term | two borrow buffers of cw words each at oW
 struct BorrowLayout {
     uint32_t lds_per_wave, oA, oB, oX, oP, oG, oW;
@@ -134,12 +146,8 @@ struct BorrowArgs {
     int mode;          // kBorrowSub / kBorrowLt / kBorrowEq
     uint32_t flip;     // comparisons: the result plus the unit polynomial (>=, <=, !=)
     uint32_t sgn;      // kBorrowLt on a signed type: bit nbits - 1 generates a_i b_i + a_i
-    BatchArg a, b, out;
-    uint64_t n;
-    uint32_t nbits;    // input bits (a comparison's output has 8)
     BorrowLayout lay;
-    int *status;
-    Bounds ab, bb, ob;
+    CircuitIO io;
 };
 
 // min / max on the same chain (kernels.hip minmax_kernel), one wavefront per
@@ -150,25 +158,18 @@ struct BorrowArgs {
 struct MinMaxArgs {
     uint32_t is_max;   // phase 2 adds a_i (max) instead of b_i (min)
     uint32_t sgn;      // signed type: bit nbits - 1 generates a_i b_i + a_i
-    BatchArg a, b, out;
-    uint64_t n;
-    uint32_t nbits;
     BorrowLayout lay;  // cw: the widest of p_i w_i and x_i w_nbits
-    int *status;
-    Bounds ab, bb, ob;
+    CircuitIO io;
 };
 
 // Oblivious choice (kernels.hip select_kernel): out_i = b_i + c x_i with c bit 0
 // of a Ciphered<bool> (its bits 1..7 are not read), one wavefront per value.  c is loaded once per
 // value; per bit a_i, b_i and x_i are formed in LDS and one product goes to the buffer at oT.
 struct SelectArgs {
-    BatchArg cond, a, b, out;
-    uint64_t n;
-    uint32_t nbits;    // bits of a, b and out (cond has 8)
+    BatchArg cond;     // (8 bits; a, b and out have io.nbits)
     uint32_t cbound;   // degree bound of cond's bit 0
-    uint32_t lds_per_wave, oC, oA, oB, oX, oT; // word offsets in a wave's LDS slice
-    int *status;
-    Bounds ab, bb, ob;
+    uint32_t lds_per_wave, oC, oA, oB, oX, oT; // word offsets in a wave's LDS slice (plan_select)
+    CircuitIO io;
 };
 
 // Table lookup (kernels.hip lookup_kernel): out = T[v] for the k <= 8 low bits v
@@ -209,9 +210,10 @@ struct LookupArgs {
 // a rotate first saves the k bits that wrap around (k slots at that stage's input bound: small,
 // because the wide steps come first).  Each product is formed in a one-bit buffer and copied to
 // its slot; the last stage whose s_t is not null sends its products to the output instead.  A
-// null s_t leaves the value where it is.  Everything below but the batches, n and status is
-// filled by shift_host.h plan_shift.  The bounds and the slot offsets travel by value: every
-// index into them is wave-uniform (dev_common.h).
+// null s_t leaves the value where it is.  Everything below but io (the amount is its second
+// operand: the low L bits of io.b, at the bounds io.bb) is filled by shift_host.h plan_shift.  The
+// bounds and the slot offsets travel by value: every index into them is wave-uniform
+// (dev_common.h).
 enum { kShiftShl = 0, kShiftShr = 1, kShiftSar = 2, kShiftRotl = 3, kShiftRotr = 4 };
 constexpr uint32_t kShiftMaxStages = 7; // log2 HM_MAX_BITS
 // The bit a stage of step k mixes into bit i of an nbits-bit value; -1: the null polynomial.
@@ -225,10 +227,8 @@ __attribute__((always_inline)) constexpr int32_t shift_src(uint32_t mode, uint32
     }
 }
 struct ShiftArgs {
-    BatchArg a, s, out; // s: the amount, read in place (its low L bits)
-    uint64_t n;
     uint32_t mode;      // kShiftShl .. kShiftRotr
-    uint32_t nbits, L;  // a power of two in 2..128 and its log2
+    uint32_t L;         // log2 io.nbits (a power of two in 2..128)
     // word offsets in a wave's LDS slice: word counts (nbits of the value's bits, 8 of the amount
     // bits, nbits / 2 of the saved bits) | the amount bits at soff[t] | x_i + x_src | the one-bit
     // product buffer | the saved bits of a rotate's stage t, sv[t] words each, at oS | the value
@@ -237,10 +237,11 @@ struct ShiftArgs {
     uint32_t sv[kShiftMaxStages];
     uint32_t soff[kShiftMaxStages];
     uint32_t off[HM_MAX_BITS];
-    uint32_t sb[kShiftMaxStages];
-    int *status;
-    Bounds ab, ob;
+    CircuitIO io;
 };
+static_assert(sizeof(ShiftArgs) < 4096 && sizeof(LookupArgs) < 4096 && sizeof(SelectArgs) < 4096 &&
+                  sizeof(BorrowArgs) < 4096 && sizeof(MinMaxArgs) < 4096 && sizeof(GateArgs) < 4096,
+              "kernarg limit");
 
 // Column-parallel carry-save multiplier (mul_engine.hip, mul_host.cpp).  Column i of
 // mul_unsigned_internal (common.rs:66-105) XORs its items x_0..x_{n-1} (the partial products

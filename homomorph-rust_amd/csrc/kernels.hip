@@ -18,10 +18,10 @@ namespace hm {
 // The launch of the wave-per-value circuits (gates, borrow chain, min / max, select, lookup,
 // shift): one wavefront per value, 4 per block, lds_per_wave words of dynamic LDS each.
 template <class Args>
-static int launch_wave_per_value(void (*kernel)(Args), const Args &g, uint32_t lds_per_wave,
-                                 void *stream) {
+static int launch_wave_per_value(void (*kernel)(Args), const Args &g, uint64_t n,
+                                 uint32_t lds_per_wave, void *stream) {
     const int wpb = 4;
-    const uint64_t blocks = (g.n + wpb - 1) / wpb;
+    const uint64_t blocks = (n + wpb - 1) / wpb;
     if (blocks == 0) return 0;
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * wpb),
                        (size_t)lds_per_wave * 4 * wpb, (hipStream_t)stream, g);
@@ -33,28 +33,24 @@ static int launch_wave_per_value(void (*kernel)(Args), const Args &g, uint32_t l
 //   AND = a*b, XOR = a+b, OR = a+b+ab, NOT = a+1    (cipher.rs:58-90)
 __global__ void __launch_bounds__(256) gate_kernel(GateArgs G) {
     extern __shared__ uint32_t lds[];
-    const int wave = (int)rfl(threadIdx.x >> 6); // wave-uniform by construction
-    const uint64_t e = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave;
-    if (e >= G.n) return;
+    const CircuitIO &IO = G.io;
+    const WaveSlice ws = wave_slice(lds, G.lds_per_wave, IO.n);
+    if (!ws.live) return;
     const int lane = lane_id();
-    uint32_t *L = lds + (size_t)wave * G.lds_per_wave;
-    uint32_t *Ab = L + G.oA, *Bb = L + G.oB, *T = L + G.oT;
-    const uint64_t *pa = G.a.limbs + e * G.a.stride;
-    const uint64_t *pb = G.op == HM_OP_NOT ? nullptr : G.b.limbs + e * G.b.stride;
-    uint64_t *po = G.out.limbs + e * G.out.stride;
-    uint32_t offa = 0, offb = 0, offo = 0;
-    for (uint32_t i = 0; i < G.nbits; ++i) {
-        const int na = load_bit(pa + offa, rfl(G.a.degree[e * G.nbits + i]), G.ab.b[i], Ab, G.status);
+    uint32_t *Ab = ws.lds + G.oA, *Bb = ws.lds + G.oB, *T = ws.lds + G.oT;
+    BitReader ra(IO.a, ws.e, IO.status), rb(IO.b, ws.e, IO.status); // (NOT: rb is not read)
+    BitWriter wo(IO.out, ws.e, IO.status);
+    for (uint32_t i = 0; i < IO.nbits; ++i) {
+        const int na = ra.load(i, IO.ab.b[i], Ab);
         int nb = 0;
         if (G.op == HM_OP_NOT) {
             if (lane == 0) Bb[0] = 1u; // the unit polynomial, CipheredBit::one (cipher.rs:49-51)
             nb = 1;
         } else {
-            nb = load_bit(pb + offb, rfl(G.b.degree[e * G.nbits + i]), G.bb.b[i], Bb, G.status);
+            nb = rb.load(i, IO.bb.b[i], Bb);
         }
         wsync();
         int nt = 0, nout;
-        const uint32_t *R = T;
         if (G.op == HM_OP_AND) {
             nt = words_of(wave_mul<kQSmall, 8>(Ab, na, Bb, nb, nullptr, 0, T, &nout));
         } else if (G.op == HM_OP_OR) {
@@ -67,17 +63,13 @@ __global__ void __launch_bounds__(256) gate_kernel(GateArgs G) {
             nt = words_of(wave_xor(Ab, na, Bb, nb, T));
         }
         wsync();
-        store_xor_bit(R, nt, nullptr, 0, po + offo, G.ob.b[i], G.out.degree + e * G.nbits + i,
-                      G.status);
+        wo.store(i, IO.ob.b[i], T, nt);
         wsync();
-        offa += cap_of(G.ab.b[i]);
-        if (G.op != HM_OP_NOT) offb += cap_of(G.bb.b[i]);
-        offo += cap_of(G.ob.b[i]);
     }
 }
 
 int launch_gate(const GateArgs &g, void *stream) {
-    return launch_wave_per_value(gate_kernel, g, g.lds_per_wave, stream);
+    return launch_wave_per_value(gate_kernel, g, g.io.n, g.lds_per_wave, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -122,58 +114,47 @@ __device__ __forceinline__ int borrow_step(const uint32_t *Ab, int na, const uin
 
 __global__ void __launch_bounds__(256) borrow_kernel(BorrowArgs G) {
     extern __shared__ uint32_t lds[];
-    const int wave = (int)rfl(threadIdx.x >> 6); // wave-uniform by construction
-    const uint64_t e = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave;
-    if (e >= G.n) return;
-    const int lane = lane_id();
+    const CircuitIO &IO = G.io;
     const BorrowLayout &Y = G.lay;
-    uint32_t *L = lds + (size_t)wave * Y.lds_per_wave;
+    const WaveSlice ws = wave_slice(lds, Y.lds_per_wave, IO.n);
+    if (!ws.live) return;
+    const int lane = lane_id();
+    uint32_t *L = ws.lds;
     uint32_t *Ab = L + Y.oA, *Bb = L + Y.oB, *X = L + Y.oX, *P = L + Y.oP, *Gt = L + Y.oG;
     uint32_t *W = L + Y.oW, *Wn = W + Y.cw;
-    const uint64_t *pa = G.a.limbs + e * G.a.stride;
-    const uint64_t *pb = G.b.limbs + e * G.b.stride;
-    uint64_t *po = G.out.limbs + e * G.out.stride;
-    uint32_t offa = 0, offb = 0, offo = 0;
+    BitReader ra(IO.a, ws.e, IO.status), rb(IO.b, ws.e, IO.status);
+    BitWriter wo(IO.out, ws.e, IO.status);
     int nw = 0; // w_0 = 0
     if (G.mode == kBorrowEq) { // e_0 = 1
         if (lane == 0) W[0] = 1u;
         nw = 1;
     }
-    for (uint32_t i = 0; i < G.nbits; ++i) {
-        const int na = load_bit(pa + offa, rfl(G.a.degree[e * G.nbits + i]), G.ab.b[i], Ab, G.status);
-        const int nb = load_bit(pb + offb, rfl(G.b.degree[e * G.nbits + i]), G.bb.b[i], Bb, G.status);
+    for (uint32_t i = 0; i < IO.nbits; ++i) {
+        const int na = ra.load(i, IO.ab.b[i], Ab);
+        const int nb = rb.load(i, IO.bb.b[i], Bb);
         wsync();
         int nx, np;
         xor_and_not(Ab, na, Bb, nb, X, P, &nx, &np);
         wsync();
         if (G.mode == kBorrowSub) {
-            store_xor_bit(X, nx, W, nw, po + offo, G.ob.b[i], G.out.degree + e * G.nbits + i,
-                          G.status);
-            offo += cap_of(G.ob.b[i]);
-            if (i + 1 == G.nbits) break; // the last borrow is not needed
+            wo.store(i, IO.ob.b[i], X, nx, W, nw);
+            if (i + 1 == IO.nbits) break; // the last borrow is not needed
         }
-        const bool top = G.sgn && i + 1 == G.nbits;
+        const bool top = G.sgn && i + 1 == IO.nbits;
         nw = borrow_step(Ab, na, Bb, nb, P, np, W, nw, Gt, Wn, G.mode != kBorrowEq, top);
         uint32_t *t = W;
         W = Wn, Wn = t;
-        offa += cap_of(G.ab.b[i]);
-        offb += cap_of(G.bb.b[i]);
     }
     if (G.mode == kBorrowSub) return;
     // Ciphered<bool>: bit 0 is the result (plus 1 for >=, <=, !=), bits 1..7 are null
     if (lane == 0) X[0] = 1u;
     wsync();
-    store_xor_bit(W, nw, X, G.flip ? 1 : 0, po, G.ob.b[0], G.out.degree + e * 8, G.status);
-    offo = cap_of(G.ob.b[0]);
-    for (uint32_t k = 1; k < 8; ++k) {
-        store_xor_bit(nullptr, 0, nullptr, 0, po + offo, G.ob.b[k], G.out.degree + e * 8 + k,
-                      G.status);
-        offo += cap_of(G.ob.b[k]);
-    }
+    wo.store(0, IO.ob.b[0], W, nw, X, G.flip ? 1 : 0);
+    for (uint32_t k = 1; k < 8; ++k) wo.store(k, IO.ob.b[k], nullptr, 0);
 }
 
 int launch_borrow(const BorrowArgs &g, void *stream) {
-    return launch_wave_per_value(borrow_kernel, g, g.lay.lds_per_wave, stream);
+    return launch_wave_per_value(borrow_kernel, g, g.io.n, g.lay.lds_per_wave, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -181,92 +162,78 @@ int launch_borrow(const BorrowArgs &g, void *stream) {
 // (min) or a_i + w_n x_i (max) with w_n kept in LDS.
 __global__ void __launch_bounds__(256) minmax_kernel(MinMaxArgs G) {
     extern __shared__ uint32_t lds[];
-    const int wave = (int)rfl(threadIdx.x >> 6); // wave-uniform by construction
-    const uint64_t e = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave;
-    if (e >= G.n) return;
+    const CircuitIO &IO = G.io;
     const BorrowLayout &Y = G.lay;
-    uint32_t *L = lds + (size_t)wave * Y.lds_per_wave;
+    const WaveSlice ws = wave_slice(lds, Y.lds_per_wave, IO.n);
+    if (!ws.live) return;
+    uint32_t *L = ws.lds;
     uint32_t *Ab = L + Y.oA, *Bb = L + Y.oB, *X = L + Y.oX, *P = L + Y.oP, *Gt = L + Y.oG;
     uint32_t *W = L + Y.oW, *Wn = W + Y.cw;
-    const uint64_t *pa = G.a.limbs + e * G.a.stride;
-    const uint64_t *pb = G.b.limbs + e * G.b.stride;
-    uint64_t *po = G.out.limbs + e * G.out.stride;
-    uint32_t offa = 0, offb = 0, offo = 0;
+    BitReader ra(IO.a, ws.e, IO.status), rb(IO.b, ws.e, IO.status);
     int nw = 0, nout; // w_0 = 0
     // phase 1: w_{i+1} = a_i b_i + b_i + p_i w_i through the top bit
-    for (uint32_t i = 0; i < G.nbits; ++i) {
-        const int na = load_bit(pa + offa, rfl(G.a.degree[e * G.nbits + i]), G.ab.b[i], Ab, G.status);
-        const int nb = load_bit(pb + offb, rfl(G.b.degree[e * G.nbits + i]), G.bb.b[i], Bb, G.status);
+    for (uint32_t i = 0; i < IO.nbits; ++i) {
+        const int na = ra.load(i, IO.ab.b[i], Ab);
+        const int nb = rb.load(i, IO.bb.b[i], Bb);
         wsync();
         int nx, np;
         xor_and_not(Ab, na, Bb, nb, X, P, &nx, &np);
         wsync();
-        nw = borrow_step(Ab, na, Bb, nb, P, np, W, nw, Gt, Wn, true, G.sgn && i + 1 == G.nbits);
+        nw = borrow_step(Ab, na, Bb, nb, P, np, W, nw, Gt, Wn, true, G.sgn && i + 1 == IO.nbits);
         uint32_t *t = W;
         W = Wn, Wn = t;
-        offa += cap_of(G.ab.b[i]);
-        offb += cap_of(G.bb.b[i]);
     }
-    // phase 2: W holds w_n; every product goes to Wn and is stored from there
-    offa = 0, offb = 0;
-    for (uint32_t i = 0; i < G.nbits; ++i) {
-        const int na = load_bit(pa + offa, rfl(G.a.degree[e * G.nbits + i]), G.ab.b[i], Ab, G.status);
-        const int nb = load_bit(pb + offb, rfl(G.b.degree[e * G.nbits + i]), G.bb.b[i], Bb, G.status);
+    // phase 2: W holds w_n; the operands from their first bit again; every product goes to Wn and
+    // is stored from there
+    ra = BitReader(IO.a, ws.e, IO.status), rb = BitReader(IO.b, ws.e, IO.status);
+    BitWriter wo(IO.out, ws.e, IO.status);
+    for (uint32_t i = 0; i < IO.nbits; ++i) {
+        const int na = ra.load(i, IO.ab.b[i], Ab);
+        const int nb = rb.load(i, IO.bb.b[i], Bb);
         wsync();
         const int nx = words_of(wave_xor(Ab, na, Bb, nb, X));
         wsync();
         const int nt = words_of(wave_mul<kQSmall, 8>(X, nx, W, nw, G.is_max ? Ab : Bb,
                                                      G.is_max ? na : nb, Wn, &nout));
         wsync();
-        store_xor_bit(Wn, nt, nullptr, 0, po + offo, G.ob.b[i], G.out.degree + e * G.nbits + i,
-                      G.status);
+        wo.store(i, IO.ob.b[i], Wn, nt);
         wsync();
-        offa += cap_of(G.ab.b[i]);
-        offb += cap_of(G.bb.b[i]);
-        offo += cap_of(G.ob.b[i]);
     }
 }
 
 int launch_minmax(const MinMaxArgs &g, void *stream) {
-    return launch_wave_per_value(minmax_kernel, g, g.lay.lds_per_wave, stream);
+    return launch_wave_per_value(minmax_kernel, g, g.io.n, g.lay.lds_per_wave, stream);
 }
 
 // Oblivious choice (SelectArgs): out_i = b_i + c x_i, c loaded once per value.
 // x_i is the uniform operand of the product (it is short when c comes out of a comparison).
 __global__ void __launch_bounds__(256) select_kernel(SelectArgs G) {
     extern __shared__ uint32_t lds[];
-    const int wave = (int)rfl(threadIdx.x >> 6); // wave-uniform by construction
-    const uint64_t e = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave;
-    if (e >= G.n) return;
-    uint32_t *L = lds + (size_t)wave * G.lds_per_wave;
+    const CircuitIO &IO = G.io;
+    const WaveSlice ws = wave_slice(lds, G.lds_per_wave, IO.n);
+    if (!ws.live) return;
+    uint32_t *L = ws.lds;
     uint32_t *C = L + G.oC, *Ab = L + G.oA, *Bb = L + G.oB, *X = L + G.oX, *T = L + G.oT;
-    const uint64_t *pa = G.a.limbs + e * G.a.stride;
-    const uint64_t *pb = G.b.limbs + e * G.b.stride;
-    uint64_t *po = G.out.limbs + e * G.out.stride;
     // bit 0 of the Ciphered<bool> is the first polynomial of the value
-    const int nc = load_bit(G.cond.limbs + e * G.cond.stride, rfl(G.cond.degree[e * 8]), G.cbound,
-                            C, G.status);
-    uint32_t offa = 0, offb = 0, offo = 0;
-    for (uint32_t i = 0; i < G.nbits; ++i) {
-        const int na = load_bit(pa + offa, rfl(G.a.degree[e * G.nbits + i]), G.ab.b[i], Ab, G.status);
-        const int nb = load_bit(pb + offb, rfl(G.b.degree[e * G.nbits + i]), G.bb.b[i], Bb, G.status);
+    const int nc = BitReader(G.cond, ws.e, IO.status).load(0, G.cbound, C);
+    BitReader ra(IO.a, ws.e, IO.status), rb(IO.b, ws.e, IO.status);
+    BitWriter wo(IO.out, ws.e, IO.status);
+    for (uint32_t i = 0; i < IO.nbits; ++i) {
+        const int na = ra.load(i, IO.ab.b[i], Ab);
+        const int nb = rb.load(i, IO.bb.b[i], Bb);
         wsync();
         const int nx = words_of(wave_xor(Ab, na, Bb, nb, X));
         wsync();
         int nout;
         const int nt = words_of(wave_mul<kQSmall, 8>(X, nx, C, nc, Bb, nb, T, &nout));
         wsync();
-        store_xor_bit(T, nt, nullptr, 0, po + offo, G.ob.b[i], G.out.degree + e * G.nbits + i,
-                      G.status);
+        wo.store(i, IO.ob.b[i], T, nt);
         wsync();
-        offa += cap_of(G.ab.b[i]);
-        offb += cap_of(G.bb.b[i]);
-        offo += cap_of(G.ob.b[i]);
     }
 }
 
 int launch_select(const SelectArgs &g, void *stream) {
-    return launch_wave_per_value(select_kernel, g, g.lds_per_wave, stream);
+    return launch_wave_per_value(select_kernel, g, g.io.n, g.lds_per_wave, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -295,22 +262,18 @@ __device__ __forceinline__ int lookup_inner_sum(const LookupArgs &G, const uint3
 
 __global__ void __launch_bounds__(256) lookup_kernel(LookupArgs G) {
     extern __shared__ uint32_t lds[];
-    const int wave = (int)rfl(threadIdx.x >> 6); // wave-uniform by construction
-    const uint64_t e = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave;
-    if (e >= G.n) return;
+    const WaveSlice ws = wave_slice(lds, G.lds_per_wave, G.n);
+    if (!ws.live) return;
     const int lane = lane_id();
-    uint32_t *L = lds + (size_t)wave * G.lds_per_wave;
+    uint32_t *L = ws.lds;
     uint32_t *N = L + G.oN, *I = L + G.oI, *P = L + G.oP, *Pn = P + G.cP;
     if (lane == 0) L[G.off[0]] = 1u, N[0] = 1u, N[16] = 1u; // ML[0] = MH[0] = 1
     // every index bit once, into its monomial's slot
-    const uint64_t *pa = G.a.limbs + e * G.a.stride;
-    uint32_t offa = 0;
+    BitReader ra(G.a, ws.e, G.status);
     for (uint32_t i = 0; i < G.k; ++i) {
         const uint32_t id = i < G.kl ? 1u << i : 16u + (1u << (i - G.kl));
-        const int na = load_bit(pa + offa, rfl(G.a.degree[e * G.a.dstride + i]), G.ab[i],
-                                L + G.off[id], G.status);
+        const int na = ra.load(i, G.ab[i], L + G.off[id]);
         if (lane == 0) N[id] = (uint32_t)na;
-        offa += cap_of(G.ab[i]);
     }
     wsync();
     // the other monomials by doubling: M[s | 1 << i] = a_i M[s], a_i the uniform operand
@@ -330,8 +293,7 @@ __global__ void __launch_bounds__(256) lookup_kernel(LookupArgs G) {
             }
         }
     }
-    uint64_t *po = G.out.limbs + e * G.out.stride;
-    uint32_t offo = 0;
+    BitWriter wo(G.out, ws.e, G.status);
     for (uint32_t j = 0; j < G.nob; ++j) {
         int np = 0; // words of the accumulator P
         for (uint32_t t = 0; t < (1u << G.kh); ++t) {
@@ -353,15 +315,13 @@ __global__ void __launch_bounds__(256) lookup_kernel(LookupArgs G) {
             uint32_t *x = P;
             P = Pn, Pn = x;
         }
-        store_xor_bit(P, np, nullptr, 0, po + offo, G.ob[j], G.out.degree + e * G.nob + j,
-                      G.status);
+        wo.store(j, G.ob[j], P, np);
         wsync();
-        offo += cap_of(G.ob[j]);
     }
 }
 
 int launch_lookup(const LookupArgs &g, void *stream) {
-    return launch_wave_per_value(lookup_kernel, g, g.lds_per_wave, stream);
+    return launch_wave_per_value(lookup_kernel, g, g.n, g.lds_per_wave, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -380,42 +340,30 @@ __device__ __forceinline__ void wave_copy(const uint32_t *Src, int n, uint32_t *
 
 __global__ void __launch_bounds__(256) shift_kernel(ShiftArgs G) {
     extern __shared__ uint32_t lds[];
-    const int wave = (int)rfl(threadIdx.x >> 6); // wave-uniform by construction
-    const uint64_t e = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave;
-    if (e >= G.n) return;
+    const CircuitIO &IO = G.io;
+    const uint32_t nbits = IO.nbits;
+    const WaveSlice ws = wave_slice(lds, G.lds_per_wave, IO.n);
+    if (!ws.live) return;
     const int lane = lane_id();
-    uint32_t *L = lds + (size_t)wave * G.lds_per_wave;
-    uint32_t *NB = L + G.oN, *NS = NB + G.nbits, *NV = NS + 8; // word counts: value, amount, saved
+    uint32_t *L = ws.lds;
+    uint32_t *NB = L + G.oN, *NS = NB + nbits, *NV = NS + 8; // word counts: value, amount, saved
     uint32_t *X = L + G.oX, *T = L + G.oT, *Sv = L + G.oS, *B = L + G.oV;
     // every bit of a into its slot, the low L bits of the amount into theirs
-    const uint64_t *pa = G.a.limbs + e * G.a.stride;
-    uint32_t offa = 0;
-    for (uint32_t i = 0; i < G.nbits; ++i) {
-        const int na = load_bit(pa + offa, rfl(G.a.degree[e * G.a.dstride + i]), G.ab.b[i],
-                                B + G.off[i], G.status);
+    BitReader ra(IO.a, ws.e, IO.status), rs(IO.b, ws.e, IO.status);
+    for (uint32_t i = 0; i < nbits; ++i) {
+        const int na = ra.load(i, IO.ab.b[i], B + G.off[i]);
         if (lane == 0) NB[i] = (uint32_t)na;
-        offa += cap_of(G.ab.b[i]);
     }
-    const uint64_t *ps = G.s.limbs + e * G.s.stride;
-    uint32_t offs = 0;
     int last = -1; // the last stage to run that is not the identity: the lowest such t
     for (uint32_t t = 0; t < G.L; ++t) {
-        const int ns = load_bit(ps + offs, rfl(G.s.degree[e * G.s.dstride + t]), G.sb[t],
-                                L + G.soff[t], G.status);
+        const int ns = rs.load(t, IO.bb.b[t], L + G.soff[t]);
         if (lane == 0) NS[t] = (uint32_t)ns;
         if (ns && last < 0) last = (int)t;
-        offs += cap_of(G.sb[t]);
     }
     wsync();
-    uint64_t *po = G.out.limbs + e * G.out.stride;
-    uint32_t *od = G.out.degree + e * G.nbits;
+    BitWriter wo(IO.out, ws.e, IO.status);
     if (last < 0) { // the amount is the null value: out = a
-        uint32_t offo = 0;
-        for (uint32_t i = 0; i < G.nbits; ++i) {
-            store_xor_bit(B + G.off[i], (int)rfl(NB[i]), nullptr, 0, po + offo, G.ob.b[i], od + i,
-                          G.status);
-            offo += cap_of(G.ob.b[i]);
-        }
+        for (uint32_t i = 0; i < nbits; ++i) wo.store(i, IO.ob.b[i], B + G.off[i], (int)rfl(NB[i]));
         return;
     }
     const bool rot = G.mode == kShiftRotl || G.mode == kShiftRotr;
@@ -428,25 +376,24 @@ __global__ void __launch_bounds__(256) shift_kernel(ShiftArgs G) {
         const bool fin = t == last; // nothing is rewritten: any order, nothing to save
         if (rot && !fin) { // the k bits that wrap: the top ones (ROTL) or the low ones (ROTR)
             for (uint32_t j = 0; j < k; ++j) {
-                const uint32_t b = down ? G.nbits - k + j : j;
+                const uint32_t b = down ? nbits - k + j : j;
                 const int nb = (int)rfl(NB[b]);
                 wave_copy(B + G.off[b], nb, Sv + j * sv);
                 if (lane == 0) NV[j] = (uint32_t)nb;
             }
             wsync();
         }
-        uint32_t offo = 0;
-        for (uint32_t q = 0; q < G.nbits; ++q) {
-            const uint32_t i = down && !fin ? G.nbits - 1 - q : q;
+        for (uint32_t q = 0; q < nbits; ++q) {
+            const uint32_t i = down && !fin ? nbits - 1 - q : q;
             uint32_t *xi = B + G.off[i];
             const int ni = (int)rfl(NB[i]);
-            const int32_t src = (int32_t)rfl((uint32_t)shift_src(G.mode, G.nbits, k, i));
+            const int32_t src = (int32_t)rfl((uint32_t)shift_src(G.mode, nbits, k, i));
             const uint32_t *V = xi; // src null: y_i = x_i + s_t x_i
             int nv = ni;
             if (src >= 0) {
                 const uint32_t *xs = B + G.off[src];
                 int nsrc = (int)rfl(NB[src]);
-                if (rot && !fin && (down ? i < k : i >= G.nbits - k)) { // src wrapped: saved
+                if (rot && !fin && (down ? i < k : i >= nbits - k)) { // src wrapped: saved
                     const uint32_t j = down ? i : (uint32_t)src;
                     xs = Sv + j * sv, nsrc = (int)rfl(NV[j]);
                 }
@@ -457,9 +404,8 @@ __global__ void __launch_bounds__(256) shift_kernel(ShiftArgs G) {
             int nout;
             const int ny = words_of(wave_mul<kQSmall, 8>(S, ns, V, nv, xi, ni, T, &nout));
             wsync();
-            if (fin) {
-                store_xor_bit(T, ny, nullptr, 0, po + offo, G.ob.b[i], od + i, G.status);
-                offo += cap_of(G.ob.b[i]);
+            if (fin) { // (i = q: in order)
+                wo.store(i, IO.ob.b[i], T, ny);
             } else {
                 wave_copy(T, ny, xi);
                 if (lane == 0) NB[i] = (uint32_t)ny;
@@ -470,7 +416,7 @@ __global__ void __launch_bounds__(256) shift_kernel(ShiftArgs G) {
 }
 
 int launch_shift(const ShiftArgs &g, void *stream) {
-    return launch_wave_per_value(shift_kernel, g, g.lds_per_wave, stream);
+    return launch_wave_per_value(shift_kernel, g, g.io.n, g.lds_per_wave, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

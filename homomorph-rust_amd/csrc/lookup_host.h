@@ -1,21 +1,19 @@
 // lookup_host.h — the table lookup's planner, host only and header only: from the plaintext table
 // and the static bounds of the index bits, the coefficient masks of every output bit (the table's
 // algebraic normal form), the table-dependent output bounds, and every plan field of LookupArgs
-// (which monomials to form, the wave's LDS layout).  No HIP, no hm_ctx, no allocation:
+// (which monomials to form, the wave's LDS layout; the word helpers and the LDS rule are
+// circuit_host.h's).  No HIP, no hm_ctx, no allocation:
 // hm_lookup_batch (capi.cpp) checks its arguments and plans here;
 // tests/sanitize/lookup_plan.cpp compiles this header alone into a stand-alone driver.
 #pragma once
 #include <stdint.h>
 #include <string.h>
 
-#include "engine.h"
+#include "circuit_host.h"
 
 namespace hm {
 namespace lookup_plan {
 
-inline uint32_t limbs_of(uint32_t bound) { return bound / 64 + 1; }
-inline uint64_t words_of(int64_t bound) { return (uint64_t)(bound / 32 + 1); }
-inline uint64_t even(uint64_t v) { return (v + 1) & ~(uint64_t)1; }
 inline uint32_t top_bit(uint32_t s) { return 31u - (uint32_t)__builtin_clz(s); } // s > 0
 
 // Entry v of a table of 2^k entries of out_nbytes little-endian bytes; bit j of it.
@@ -106,12 +104,13 @@ inline hm_status plan_lookup(uint32_t k, const uint32_t *a_bound, uint32_t out_n
         for (uint32_t s = 1; s < (1u << kk); ++s) {
             const uint32_t top = top_bit(s), rest = s ^ (1u << top), b = a_bound[base + top];
             sum[s] = sum[rest] + b;
-            const uint64_t cap = rest ? words_of(sum[rest]) + words_of(b) : 2 * (uint64_t)limbs_of(b);
+            const uint64_t cap = rest ? (uint64_t)words_of_bound(sum[rest]) + words_of_bound(b)
+                                      : 2 * (uint64_t)cap_of(b);
             if (o + cap > 0xFFFFFFFFu) return HM_ERR_UNSUPPORTED;
             A.off[16 * half + s] = (uint32_t)o;
             o += even(cap);
             uint64_t &widest = half ? cH : cI;
-            if (words_of(sum[s]) > widest) widest = words_of(sum[s]);
+            if (words_of_bound(sum[s]) > widest) widest = words_of_bound(sum[s]);
         }
     }
     const uint64_t cP = even(cI + cH) + 2; // an accumulator: MH[t] I_jt, or an inner sum alone
@@ -119,8 +118,7 @@ inline hm_status plan_lookup(uint32_t k, const uint32_t *a_bound, uint32_t out_n
     if (total > 0xFFFFFFFFu) return HM_ERR_UNSUPPORTED;
     A.oI = (uint32_t)oI, A.oP = (uint32_t)oP, A.cI = (uint32_t)cI, A.cP = (uint32_t)cP;
     A.lds_per_wave = (uint32_t)total;
-    // four waves' slices within a CU's LDS, as the sibling circuits (capi.cpp run_circuit)
-    return (uint64_t)A.lds_per_wave * 16 > 160 * 1024 ? HM_ERR_UNSUPPORTED : HM_OK;
+    return lds_status(A.lds_per_wave);
 }
 
 } // namespace hm

@@ -7,7 +7,7 @@
 #include <stdint.h>
 #include <string.h>
 
-#include "engine.h"
+#include "circuit_host.h"
 
 namespace hm {
 namespace shift_plan {
@@ -51,37 +51,31 @@ inline hm_status bounds(hm_op which, uint32_t nbits, const uint32_t *a_bound,
     return HM_OK;
 }
 
-inline uint32_t limbs_of(uint32_t bound) { return bound / 64 + 1; }
-inline uint64_t even(uint64_t v) { return (v + 1) & ~(uint64_t)1; }
-
 } // namespace shift_plan
 
 // Every plan field of ShiftArgs from the input bounds and the output bounds need (shift_plan::
-// bounds); the batches, n, status and the output batch's own bounds (ob) are the caller's.  The
-// caller has checked nbits (shift_plan::stages).  HM_ERR_UNSUPPORTED: four waves' slices do not
+// bounds); the I/O block (the batches and their own bounds) is the caller's.  The caller has
+// checked nbits (shift_plan::stages).  HM_ERR_UNSUPPORTED: four waves' slices do not
 // fit a CU's LDS.
 inline hm_status plan_shift(uint32_t mode, uint32_t nbits, const uint32_t *a_bound,
                             const uint32_t *s_bound, const uint32_t *need, ShiftArgs &A) {
     using namespace shift_plan;
     const uint32_t L = stages(nbits);
-    A.mode = mode, A.nbits = nbits, A.L = L;
-    memset(A.ab.b, 0, sizeof(A.ab.b)), memset(A.sb, 0, sizeof(A.sb));
+    A.mode = mode, A.L = L;
     memset(A.off, 0, sizeof(A.off)), memset(A.soff, 0, sizeof(A.soff));
-    for (uint32_t i = 0; i < nbits; ++i) A.ab.b[i] = a_bound[i];
     // layout, in words.  An input bit's slot holds whole limbs (load_bit); a product's buffer its
     // factors' words at their bounds (wave_mul writes nu + nv <= bound / 32 + 2 words), and so
     // does a slot, which covers the limbs of its input bit (need[i] >= a_bound[i]).
     uint64_t o = 0;
-    A.oN = 0, o = shift_plan::even((uint64_t)nbits + 8 + nbits / 2);
+    A.oN = 0, o = even((uint64_t)nbits + 8 + nbits / 2);
     for (uint32_t t = 0; t < L; ++t) {
-        A.sb[t] = s_bound[t];
         A.soff[t] = (uint32_t)o;
-        o += 2 * (uint64_t)limbs_of(s_bound[t]);
+        o += 2 * (uint64_t)cap_of(s_bound[t]);
     }
     uint64_t cV = 0, widest = 2;
     uint32_t amax = 0;
     for (uint32_t i = 0; i < nbits; ++i) {
-        const uint64_t slot = shift_plan::even((uint64_t)need[i] / 32 + 2);
+        const uint64_t slot = even((uint64_t)need[i] / 32 + 2);
         A.off[i] = (uint32_t)cV;
         cV += slot;
         widest = slot > widest ? slot : widest;
@@ -93,7 +87,7 @@ inline hm_status plan_shift(uint32_t mode, uint32_t nbits, const uint32_t *a_bou
     memset(A.sv, 0, sizeof(A.sv));
     for (uint32_t t = L; t-- > 0;) {
         if (mode == kShiftRotl || mode == kShiftRotr) {
-            A.sv[t] = (uint32_t)shift_plan::even((above + amax) / 32 + 2);
+            A.sv[t] = (uint32_t)even((above + amax) / 32 + 2);
             const uint64_t area = ((uint64_t)1 << t) * A.sv[t];
             save = area > save ? area : save;
         }
@@ -104,8 +98,7 @@ inline hm_status plan_shift(uint32_t mode, uint32_t nbits, const uint32_t *a_bou
     A.oX = (uint32_t)oX, A.oT = (uint32_t)oT, A.oS = (uint32_t)oS, A.oV = (uint32_t)oV;
     A.cV = (uint32_t)cV;
     A.lds_per_wave = (uint32_t)total;
-    // four waves' slices within a CU's LDS, as the sibling circuits (capi.cpp run_circuit)
-    return (uint64_t)A.lds_per_wave * 16 > 160 * 1024 ? HM_ERR_UNSUPPORTED : HM_OK;
+    return lds_status(A.lds_per_wave);
 }
 
 } // namespace hm

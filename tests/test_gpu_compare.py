@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 
 import borrow_model as bm
-from helpers import as_bytes, assert_batches_equal, bit_ints, keys, masks, plain
+from circuit_gpu import encrypt_both, load_engine, make_world
+from helpers import assert_batches_equal, plain
 
 pytestmark = pytest.mark.gpu
 
@@ -22,27 +23,12 @@ SEED = 2025
 
 @pytest.fixture(scope="module")
 def H():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import homomorph
-    homomorph.lib()  # loud failure if the engine is not built
-    return homomorph
+    return load_engine()
 
 
 @pytest.fixture(scope="module")
 def world(H, oracle):
-    """Contexts and oracle keys per parameter set, made once (same seed on both sides)."""
-    cache = {}
-
-    def get(params):
-        if params not in cache:
-            ctx = H.Context(H.Parameters(*params))
-            ctx.seed_rng(SEED)
-            ctx.generate_secret_key()
-            ctx.generate_public_key()
-            cache[params] = (ctx, keys(*params, SEED))
-        return cache[params]
-    return get
+    return make_world(H, SEED)
 
 
 def op_class(H, op):
@@ -61,21 +47,6 @@ def edge_pairs(udt):
     rows = [(v, v), (v | 1, (v | 1) + 1), (v, v | 1), (v & ~top, v | top), (0, info.max),
             (top, top - 1), (info.max, 0)]
     return np.array([r[0] for r in rows], udt), np.array([r[1] for r in rows], udt)
-
-
-def encrypt_both(H, oracle, world, params, vals, mask_seed, bound=None, zero_masks=False):
-    """(device batch, its model polynomials per value) of one operand."""
-    ctx, (sk, pk, _) = world(params)
-    nbits = 8 * vals.dtype.itemsize
-    n = len(vals)
-    m = masks(n, nbits, params[3], mask_seed)
-    if zero_masks:
-        m[:] = 0
-    if bound is None:
-        bound = np.full(nbits, params[0] + params[1], np.uint32)
-    dev = ctx.encrypt(vals, masks=m, bound=bound)
-    l, d = oracle.encrypt_batch(pk, as_bytes(vals), m, bound)
-    return dev, [bit_ints(l, d, bound, e) for e in range(n)]
 
 
 def check_all(H, world, params, a, A, av, b, B, bv, what):

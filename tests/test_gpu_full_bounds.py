@@ -105,8 +105,8 @@ def _cmp(H, op):
 @pytest.mark.parametrize("what", ["sub", "unsigned", "signed"])
 @pytest.mark.parametrize("name", list(synth.BORROW_CASES))
 def test_sub_and_comparisons(H, world, name, what):
-    """borrow_kernel (kernels.hip) in borrow_run's LDS layout (capi.cpp: SA, SB, SX = 2 cap words,
-    two borrow buffers of cw = SX + chain / 32 + 3): the generate product wave_mul<kQSmall, 8>(a_i,
+    """borrow_kernel (kernels.hip) in plan_borrow's LDS layout (circuit_host.h: SA, SB, SX = 2 cap
+    words, two borrow buffers of cw = SX + chain / 32 + 3): the generate product wave_mul<kQSmall, 8>(a_i,
     na, b_i, nb, ...) and the propagate product wave_mul<kQSmall, 8>(p_i, np, w_i, nw, ...).
     Paths (synth.check_borrow_path):
       u8_b700       uniform 700: na = 22 (3 kQSmall chunks), p_i of 22 words = its slot SX, and

@@ -10,12 +10,15 @@ path, a last stage that is not stage 0), an amount read in place from a wider ba
 than lanes, a batch that is no multiple of a block's four waves.
 """
 import ctypes
+import functools
 
 import numpy as np
 import pytest
 
+import circuit_gpu
 import shift_model as sm
-from helpers import as_bytes, assert_batches_equal, bit_ints, keys, masks, plain
+from circuit_gpu import load_engine, make_world
+from helpers import assert_batches_equal, bit_ints, plain
 
 gpu = pytest.mark.gpu
 
@@ -26,27 +29,12 @@ SEED = 2026
 
 @pytest.fixture(scope="module")
 def H():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import homomorph
-    homomorph.lib()  # loud failure if the engine is not built
-    return homomorph
+    return load_engine()
 
 
 @pytest.fixture(scope="module")
 def world(H, oracle):
-    """Contexts and oracle keys per parameter set, made once (same seed on both sides)."""
-    cache = {}
-
-    def get(params):
-        if params not in cache:
-            ctx = H.Context(H.Parameters(*params))
-            ctx.seed_rng(SEED)
-            ctx.generate_secret_key()
-            ctx.generate_public_key()
-            cache[params] = (ctx, keys(*params, SEED))
-        return cache[params]
-    return get
+    return make_world(H, SEED)
 
 
 def marker(H, op):
@@ -54,20 +42,7 @@ def marker(H, op):
             "rotl": H.HomomorphicRotateLeft, "rotr": H.HomomorphicRotateRight}[op]
 
 
-def encrypt_both(H, oracle, world, params, vals, mask_seed, bound=None, zero_masks=False):
-    """(device batch, its model polynomials per value) of one operand; vals: an integer array, or
-    the (n, nbytes) little-endian bytes of wider values."""
-    ctx, (sk, pk, _) = world(params)
-    raw = vals if vals.ndim == 2 else as_bytes(vals)
-    n, nbits = raw.shape[0], 8 * raw.shape[1]
-    m = masks(n, nbits, params[3], mask_seed)
-    if zero_masks:
-        m[:] = 0
-    if bound is None:
-        bound = np.full(nbits, params[0] + params[1], np.uint32)
-    dev = ctx.encrypt(vals, masks=m, bound=bound)
-    l, d = oracle.encrypt_batch(pk, raw, m, bound)
-    return dev, [bit_ints(l, d, bound, e) for e in range(n)]
+encrypt_both = functools.partial(circuit_gpu.encrypt_both, wide=True)  # (u64, u128 as bytes)
 
 
 def assert_equals_model(out, values, what):
