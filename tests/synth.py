@@ -401,6 +401,36 @@ DEC_CASES = {
 }
 DEC_N = 64
 
+# The cipher-paths tier's decryption cases (cipher_paths.py, test_gpu_cipher_paths.py), named for
+# the kernel and branch they reach (check_dec_path): name -> (per-bit bounds, n).  A bit of
+# capacity C has bound 64 C - 1, so a polynomial that fills it has its top coefficient in the
+# last bit of the bit's last limb.
+DEC_WIDE_BITS = {0: 193, 1: 255, 62: 256, 63: 257, 64: 449, 65: 512, 127: 513}  # bit -> limbs
+
+
+def _dec_wide128():
+    cap = [1 + i % 4 for i in range(128)]
+    for i, c in DEC_WIDE_BITS.items():
+        cap[i] = c
+    return u32([64 * c - 1 for c in cap])
+
+
+DEC_PATH_CASES = {f"bits_ucap_c{C}_n{n}": (uniform(8, 64 * C - 1), n)
+                  for C in (1, 8) for n in (1, 3, 9)}
+DEC_PATH_CASES.update({
+    "bits_ucap_c1_16byte_n3": (uniform(128, 63), 3),
+    "bits_ucap_c8_16byte_n3": (uniform(128, 511), 3),
+    # capacity 1 + (i + i / 32) mod 32: each of 1 .. 32 at four bits whose scheduled kinds differ
+    "bits_general_16byte_caps1_32_n3": (u32([64 * (1 + (i + i // 32) % 32) - 1 for i in range(128)]), 3),
+    "wave_16byte_wide_n5": (_dec_wide128(), 5),
+    "wave_u8_cap512_n6": (uniform(8, 64 * 512 - 1), 6),
+})
+
+
+def _dec_spec(name):
+    """(per-bit bounds, n) of a decryption case of either table."""
+    return (DEC_CASES[name], DEC_N) if name in DEC_CASES else DEC_PATH_CASES[name]
+
 
 def _seed(family, name):
     return SEED + sum(ord(c) * (k + 1) for k, c in enumerate(family + "/" + name)) % 100000
@@ -422,8 +452,8 @@ def inputs(family, name):
         ba, bb = MUL_CLASS_CASES[name]["ba"], MUL_CLASS_CASES[name]["bb"]
         ns, npair = 8, 2
     elif family == "dec":
-        ba = bb = DEC_CASES[name]
-        ns, npair = DEC_N, 0
+        ba, ns = _dec_spec(name)
+        bb, npair = ba, 0
     else:
         raise KeyError(family)
     if family == "mulc" and name in MUL_LADDERS:
@@ -556,10 +586,13 @@ def mul_census(name, mfma=True):
 @functools.lru_cache(maxsize=None)
 def dec_reference(name):
     """The plaintext bytes of the case's operand a under the DEC_PARAMS key (the model's
-    decipher_bit; test_synth_reference.py pins it to oracle.decrypt_batch)."""
+    decipher_bit; test_synth_reference.py and test_cipher_paths.py pin it to
+    oracle.decrypt_batch): (n, nbits / 8) uint8, a value's bytes little-endian."""
     c = inputs("dec", name)
     s, _ = model.keygen(*DEC_PARAMS, SEED)
-    out = np.array([[bm.decrypt_value(bits, s)] for bits in c["A"]], dtype=np.uint8)
+    nbytes = c["nbits"] // 8
+    out = np.array([list(bm.decrypt_value(bits, s).to_bytes(nbytes, "little")) for bits in c["A"]],
+                   dtype=np.uint8)
     out.setflags(write=False)
     return out
 
@@ -833,6 +866,8 @@ def _check_ladder(name, c, cen, nua):
 
 def check_dec_path(name):
     """hm_decrypt_batch: D.ucap = the common capacity when all are equal and <= 8 limbs."""
+    if name in DEC_PATH_CASES:
+        return _check_dec_path_case(name)
     c = inputs("dec", name)
     caps = (c["ba"] // 64 + 1).tolist()
     ucap = caps[0] if len(set(caps)) == 1 and caps[0] <= 8 else 0
@@ -846,3 +881,52 @@ def check_dec_path(name):
     for i in range(8):  # some polynomial reaches the last bit of every bit's capacity-defining bound
         assert max(v[i].bit_length() - 1 for v in c["A"]) == int(c["ba"][i])
     return dict(ucap=ucap)
+
+
+def _check_dec_path_case(name):
+    """The DEC_PATH_CASES, against cipher_paths.dec_dispatch (launch_decrypt: `D.maxcap <= 32` picks
+    decrypt_bits_kernel, whose `if (D.ucap)` path stages 64 C limbs per wave in LDS; else
+    decrypt_kernel, whose 4-way unrolled body runs while `k + (kDecUnroll - 1) * kWave < cap`)."""
+    import cipher_paths as cp
+    c = inputs("dec", name)
+    caps = (c["ba"] // 64 + 1).tolist()
+    d = cp.dec_dispatch(c["ba"], c["n"])
+    top = lambda i: max(v[i].bit_length() - 1 for v in c["A"]) == int(c["ba"][i])  # noqa: E731
+    # some polynomial reaches the top coefficient of every capacity the host sizes a slot by
+    for cap in set(caps):
+        assert any(top(i) for i in range(c["nbits"]) if caps[i] == cap), (name, cap)
+    if name.startswith("bits_ucap"):
+        C = int(name.split("_c")[1].split("_")[0])
+        assert d["kernel"] == "decrypt_bits_kernel" and d["ucap"] == C and caps == [C] * c["nbits"]
+        total = c["n"] * c["nbits"]
+        if "16byte" in name:  # 384 bits: a whole block of four waves and half of the next
+            assert c["nbits"] == 128 and total == 384 and d["blocks"] == 2 and not d["partial_wave"]
+        else:  # 8, 24, 72 bits: below one wave, and one wave + 8 bits
+            assert total == {1: 8, 3: 24, 9: 72}[c["n"]] and d["partial_wave"]
+    elif name == "bits_general_16byte_caps1_32_n3":
+        # both HM_MAX_BITS LDS arrays (bounds, offsets) full; the last capacity of the kernel
+        assert d["kernel"] == "decrypt_bits_kernel" and d["ucap"] == 0 and c["nbits"] == 128
+        assert set(caps) == set(range(1, 33)) and max(caps) == cp.DEC_BITS_MAXCAP
+    elif name == "wave_16byte_wide_n5":
+        assert d["kernel"] == "decrypt_kernel" and d["partial_block"] and d["blocks"] == 2
+        assert {caps[i] for i in DEC_WIDE_BITS} == {193, 255, 256, 257, 449, 512, 513}
+        assert max(caps[i] for i in range(128) if i not in DEC_WIDE_BITS) == 4
+        # (lanes entering the unrolled body, its rounds on lane 0, tail rounds on lanes 0 and 63)
+        assert [cp.dec_wave_trace(caps[i]) for i in sorted(DEC_WIDE_BITS)] == [
+            (1, 1, 0, 3), (63, 1, 0, 3), (64, 1, 0, 0), (64, 1, 1, 0), (64, 2, 0, 3),
+            (64, 2, 0, 0), (64, 2, 1, 0)]
+        assert cp.dec_wave_trace(4) == (0, 0, 1, 0)
+        # bits 0 .. 63 go to m0 and 64 .. 127 to m1: wide bits on both sides of the seam, with
+        # FULL, ONES and MONO polynomials at the top coefficient of each
+        for i in (0, 63, 64, 127):
+            kinds = {kind_of(e, i) for e in range(c["n"])}
+            assert {"FULL", "ONES", "MONO"} <= kinds, (i, kinds)
+            b = int(c["ba"][i])
+            assert any(v[i] == 1 << b for v in c["A"]) and any(v[i] == (1 << (b + 1)) - 1 for v in c["A"])
+        assert all(top(i) for i in DEC_WIDE_BITS)
+    elif name == "wave_u8_cap512_n6":
+        assert d["kernel"] == "decrypt_kernel" and d["partial_block"] and caps == [512] * 8
+        assert cp.dec_wave_trace(512) == (64, 2, 0, 0) and all(top(i) for i in range(8))
+    else:
+        raise KeyError(name)
+    return d

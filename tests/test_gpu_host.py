@@ -55,10 +55,12 @@ def test_unseeded_keys_and_masks_are_fresh(H):
                                             ((128, 128, 1, 128), np.uint32, 40000)])
 def test_engine_masks_reproduce_with_seed(H, oracle, params, dtype, n):
     """Engine-drawn masks under a seed are the seeded ChaCha20 bytes: the oracle, fed those
-    bytes, produces the identical ciphertexts.  At tau = 128 the masks are drawn inside the
-    encryption kernel (encrypt_chacha_kernel: 256 bits per wave, a partial last slice at
-    n = 41; n = 40000 takes several grid strides, checked on sampled values); the second
-    encryption uses the next nonce."""
+    bytes, produces the identical ciphertexts.  The masks are drawn by rand_fill_kernel (one
+    64-byte ChaCha20 block per thread) into the context's mask buffer right before the
+    encryption kernel, which then advances the nonce itself (enc_nonce_bump: no bump launch);
+    n = 41 ends on a partly filled wave, n = 40000 takes several grid strides of
+    encrypt_table_kernel<5,32,TOP1> and is checked on sampled values; the second encryption
+    uses the next nonce."""
     ctx = H.Context(H.Parameters(*params))
     ctx.seed_rng(77)
     ctx.generate_secret_key()
