@@ -5,7 +5,8 @@
 // 310-323; Parameters::new asserts, :87-94) and launches the kernels.  The static degree bounds
 // and the plans come from host-only headers: the adder's from add_host.h (plan_add), the
 // wave-per-value circuits' from circuit_host.h (plan_gate, plan_borrow, plan_select),
-// lookup_host.h (plan_lookup) and shift_host.h (plan_shift); the multiplier's from mul_host.cpp.
+// lookup_host.h (plan_lookup), shift_host.h (plan_shift) and bitcount_host.h (plan_bitcount); the
+// multiplier's from mul_host.cpp.
 // Never throws across the ABI.
 #include <hip/hip_runtime.h>
 
@@ -20,6 +21,7 @@
 #include <sys/random.h>
 
 #include "add_host.h"
+#include "bitcount_host.h"
 #include "circuit_host.h"
 #include "ctx.h"
 #include "lookup_host.h"
@@ -111,8 +113,8 @@ uint16_t min_d_over_delta(hm_op op) { // src/impls/numbers.rs:27-50
     case HM_OP_ADD: return 21;
     case HM_OP_MUL: case HM_OP_MUL_SIGNED: return 64;
     case HM_OP_SELECT: return 5; // 2m + 1 for c x_i of fresh bits, m = 2
-    default: break; // HM_OP_SUB .. HM_OP_GE, HM_OP_MIN, HM_OP_MAX, HM_OP_LOOKUP and the shifts
-                    // depend on the width: borrow_min_d_over_delta
+    default: break; // HM_OP_SUB .. HM_OP_GE, HM_OP_MIN, HM_OP_MAX, HM_OP_LOOKUP, the shifts and
+                    // the bit counts depend on the width: borrow_min_d_over_delta
     }
     return 0xFFFF;
 }
@@ -122,19 +124,23 @@ bool is_compare_op(hm_op op) { return op >= HM_OP_EQ && op <= HM_OP_GE; }
 bool is_ordering_op(hm_op op) { return op >= HM_OP_LT && op <= HM_OP_GE; }
 bool is_minmax_op(hm_op op) { return op == HM_OP_MIN || op == HM_OP_MAX; }
 using shift_plan::is_shift_op;
+using bitcount_plan::is_bitcount_op;
 bool needs_width(hm_op op) {
-    return is_borrow_op(op) || is_minmax_op(op) || op == HM_OP_LOOKUP || is_shift_op(op);
+    return is_borrow_op(op) || is_minmax_op(op) || op == HM_OP_LOOKUP || is_shift_op(op) ||
+           is_bitcount_op(op);
 }
 
 // 2m + 1 with m the borrow circuit's degree in fresh input bits: nbits + 1 for the orderings
 // (the borrow out of the top bit), nbits for subtraction and equality, nbits + 2 for min / max
 // (that borrow times x_i).  A table lookup is multilinear in its nbits index bits: m = nbits.
 // A shift or rotate of an nbits-bit value is log2 nbits selects deep: m = log2 nbits + 1 (the
-// caller has checked the width, shift_plan::stages).
+// caller has checked the width, shift_plan::stages).  A bit count's m is bitcount_plan::degree_of:
+// the top symmetric polynomial 2^floor(log2 nbits) of a count, the whole prefix nbits of a run.
 // A fresh bit's noise has degree delta + 1 <= 2 delta, so d >= (2m + 1) delta gives
 // m (delta + 1) < d.
 uint16_t borrow_min_d_over_delta(hm_op op, uint32_t nbits) {
     if (is_shift_op(op)) return (uint16_t)(2 * shift_plan::stages(nbits) + 3);
+    if (is_bitcount_op(op)) return (uint16_t)(2 * bitcount_plan::degree_of(op, nbits) + 1);
     const uint32_t m = nbits + (is_ordering_op(op) ? 1u : is_minmax_op(op) ? 2u : 0u);
     return (uint16_t)(2 * m + 1);
 }
@@ -736,6 +742,14 @@ hm_status hm_shift_out_bounds(hm_op which, uint32_t nbits, const uint32_t *a, co
     return shift_plan::bounds(which, nbits, a, s, out);
 } HM_ABI_CATCH
 
+// Degree bounds of a bit count.
+hm_status hm_bitcount_out_bounds(hm_op which, uint32_t nbits, const uint32_t *a,
+                                 uint32_t out[8]) try {
+    if (!a || !out || !is_bitcount_op(which) || nbits == 0 || nbits > HM_MAX_BITS)
+        return HM_ERR_INVALID_ARGUMENT;
+    return bitcount_plan::bounds(which, nbits, a, out);
+} HM_ABI_CATCH
+
 hm_status hm_minmax_out_bounds(uint32_t L, const uint32_t *a, const uint32_t *b,
                                uint32_t *out) try {
     if (!a || !b || !out || L == 0 || L > HM_MAX_BITS) return HM_ERR_INVALID_ARGUMENT;
@@ -1094,6 +1108,20 @@ hm_status hm_shift_batch(hm_ctx *c, hm_op which, const hm_batch *a, const hm_bat
         return st;
     fill_io(G.io, c, a, amount, out);
     return run_circuit(c, G, launch_shift);
+} HM_ABI_CATCH
+
+hm_status hm_bitcount_batch(hm_ctx *c, hm_op which, const hm_batch *a, hm_batch *out) try {
+    if (!c || !a || !out || !is_bitcount_op(which)) return HM_ERR_INVALID_ARGUMENT;
+    if (hm_status st = check_operands({{a, 0}, {out, kBitCountOut}}); st) return st;
+    if (hm_status st = hm_validate_operation_bits(c, which, a->nbits, nullptr); st) return st;
+    std::vector<uint32_t> need(kBitCountOut);
+    if (hm_status st = bitcount_plan::bounds(which, a->nbits, a->bound, need.data()); st) return st;
+    if (!covers(out, need) || overlaps(out, a)) return HM_ERR_INVALID_ARGUMENT;
+    if (a->n == 0) return HM_OK;
+    BitCountArgs G{};
+    if (hm_status st = plan_bitcount(which, a->nbits, a->bound, G); st) return st;
+    fill_io(G.io, c, a, nullptr, out);
+    return run_circuit(c, G, bitcount_plan::is_run_op(which) ? launch_bitrun : launch_bitcount);
 } HM_ABI_CATCH
 
 // ------------------------------------------------------------------ polynomial primitives

@@ -151,6 +151,12 @@ struct BitReader {
         off += cap_of(bound);
         return n;
     }
+    // the same from the top bit down: bit i is the one BEFORE the last loaded (the caller sets off
+    // to the value's limbs before the first)
+    __device__ __forceinline__ int load_down(uint32_t i, uint32_t bound, uint32_t *dst) {
+        off -= cap_of(bound);
+        return load_bit(limbs + off, rfl(degree[i]), bound, dst, status);
+    }
 };
 struct BitWriter {
     uint64_t *limbs;

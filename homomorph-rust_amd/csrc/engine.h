@@ -111,9 +111,10 @@ struct DecArgs {
     KTimer kt;
 };
 
-// The wave-per-value circuits (kernels.hip: gates, borrow chain, min / max, select, lookup, shift)
-// keep their intermediates in LDS, one wavefront per value, in a slice of lds_per_wave words whose
-// layout the host plans (circuit_host.h, lookup_host.h, shift_host.h).  What their argument
+// The wave-per-value circuits (kernels.hip: gates, borrow chain, min / max, select, lookup, shift,
+// bit counts) keep their intermediates in LDS, one wavefront per value, in a slice of lds_per_wave
+// words whose layout the host plans (circuit_host.h, lookup_host.h, shift_host.h,
+// bitcount_host.h).  What their argument
 // blocks share, filled by capi.cpp fill_io: the operands, the output and their static bounds.
 struct CircuitIO {
     BatchArg a, b, out; // b: the second operand (a shift's amount; a unary gate has none)
@@ -239,8 +240,46 @@ struct ShiftArgs {
     uint32_t off[HM_MAX_BITS];
     CircuitIO io;
 };
+// Bit counts (kernels.hip bitcount_kernel and bitrun_kernel): count_ones /
+// count_zeros and the leading / trailing runs of an n-bit value as a Ciphered<u8>, one wavefront
+// per value.  Both work on literals u_i = x_i (the "ones" ops) or x_i + 1 (zeros).
+//   counts  out_k = e_{2^k}(u_0 .. u_{n-1}), the elementary symmetric polynomial, by the recurrence
+//           E_j <- E_j + u_i E_{j-1} (j descending, E_0 = 1), one literal after another.  E_j lives
+//           in slot j <= J of the wave's LDS slice; for n a power of two the top target e_n is the
+//           running product of all literals, kept past J in two ping-pong buffers (the diagonal).
+//           An update runs only while bitcount_needed says some target still reads its result.
+//   runs    the literals in the run's order (leading: from the top bit down), t_j = v_1 .. v_j in
+//           two ping-pong buffers, out_k = the sum of t_{m 2^k}: one accumulator per output bit.
+// Everything below but io (a is its first operand; it has no second) is filled by bitcount_host.h
+// plan_bitcount.  The slot offsets travel by value: every index into them, as into io.ab and
+// io.ob, is wave-uniform (dev_common.h).
+constexpr uint32_t kBitCountMaxSlots = HM_MAX_BITS / 2; // E_1 .. E_64 (n = 65 .. 128)
+constexpr uint32_t kBitCountOut = 8;                    // bits of the Ciphered<u8>
+// After i literals of n, is E_j (1 <= j <= i) still read by some target T = 2^k <= n?  The
+// recurrence reaches E_T^(n) from E_j^(i) only over j <= T with T - j of the n - i literals left.
+__attribute__((always_inline)) constexpr bool bitcount_needed(uint32_t n, uint32_t i, uint32_t j) {
+    for (uint32_t T = 1; T <= n; T <<= 1)
+        if (j <= T && T - j <= n - i) return true;
+    return false;
+}
+struct BitCountArgs {
+    uint32_t zeros;    // the literal is x_i + 1
+    uint32_t leading;  // runs: the literals from the top bit down
+    uint32_t K;        // output bits that are not null by rule: floor(log2 n) + 1
+    uint32_t J;        // counts: slots E_1 .. E_J (n / 2 for a power of two n >= 2, else 2^(K-1))
+    uint32_t diag;     // counts: the target 2^(K-1) = n is the running product, past slot J
+    uint32_t a_limbs;  // limbs of one value of a (a leading run reads its bits from the top down)
+    // word offsets in a wave's LDS slice: word counts (kBitCountMaxSlots + 1 of the slots, 8 of the
+    // accumulators) | the literal | the product buffer (counts) | two ping-pong buffers of cD words
+    // each (the diagonal, the run's prefix) | the slots E_j at off[j] (counts), the accumulators
+    // of output bit k at off[k] (runs), from oE
+    uint32_t lds_per_wave, oN, oU, oT, oD, cD, oE;
+    uint32_t off[kBitCountMaxSlots + 1];
+    CircuitIO io;
+};
 static_assert(sizeof(ShiftArgs) < 4096 && sizeof(LookupArgs) < 4096 && sizeof(SelectArgs) < 4096 &&
-                  sizeof(BorrowArgs) < 4096 && sizeof(MinMaxArgs) < 4096 && sizeof(GateArgs) < 4096,
+                  sizeof(BorrowArgs) < 4096 && sizeof(MinMaxArgs) < 4096 && sizeof(GateArgs) < 4096 &&
+                  sizeof(BitCountArgs) < 4096,
               "kernarg limit");
 
 // Column-parallel carry-save multiplier (mul_engine.hip, mul_host.cpp).  Column i of
@@ -527,6 +566,8 @@ int launch_minmax(const MinMaxArgs &a, void *stream);
 int launch_select(const SelectArgs &a, void *stream);
 int launch_lookup(const LookupArgs &a, void *stream);
 int launch_shift(const ShiftArgs &a, void *stream);
+int launch_bitcount(const BitCountArgs &a, void *stream); // count_ones, count_zeros
+int launch_bitrun(const BitCountArgs &a, void *stream);   // leading / trailing zeros / ones
 int launch_mul_stage(const MulStageArgs &a, void *stream);
 int launch_mul_pp(const MulPPArgs &a, void *stream);
 int launch_mul_scan(const MulScanArgs &a, void *stream);

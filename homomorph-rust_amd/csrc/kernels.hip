@@ -7,6 +7,7 @@
 //   select_kernel   cond ? a : b on an encrypted bool (s4.4b)
 //   lookup_kernel   T[v] for a plaintext table T and an encrypted index of up to 8 bits (s4.4c)
 //   shift_kernel    <<, >>, rotates by an encrypted amount: a barrel shifter in LDS (s4.4d)
+//   bitcount_kernel, bitrun_kernel   count_ones / count_zeros; leading / trailing runs (s4.4e)
 //   poly_* kernels single-polynomial primitives for unit parity (polynomial.rs:190-365)
 // (adder: adder.hip; cipher: cipher.hip; carry-save multiplier: mul_engine.hip)
 #include <hip/hip_runtime.h>
@@ -16,7 +17,7 @@
 namespace hm {
 
 // The launch of the wave-per-value circuits (gates, borrow chain, min / max, select, lookup,
-// shift): one wavefront per value, 4 per block, lds_per_wave words of dynamic LDS each.
+// shift, bit counts): one wavefront per value, 4 per block, lds_per_wave words of dynamic LDS each.
 template <class Args>
 static int launch_wave_per_value(void (*kernel)(Args), const Args &g, uint64_t n,
                                  uint32_t lds_per_wave, void *stream) {
@@ -417,6 +418,139 @@ __global__ void __launch_bounds__(256) shift_kernel(ShiftArgs G) {
 
 int launch_shift(const ShiftArgs &g, void *stream) {
     return launch_wave_per_value(shift_kernel, g, g.io.n, g.lds_per_wave, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Bit counts (BitCountArgs): count_ones / count_zeros as the elementary symmetric
+// polynomials e_{2^k} of the literals, the leading / trailing runs as sums over the literals'
+// prefix products.  The literal u_i, the short operand, is the uniform one of every product; a
+// null factor skips its product on a scalar branch.
+
+// The literal of the bit just loaded into U (nx words, 0: null, U[0] then undefined): the bit
+// itself, or for the zeros ops the bit plus the unit polynomial.  Returns its words.
+__device__ __forceinline__ int bitcount_literal(uint32_t *U, int nx, bool zeros) {
+    if (!zeros) return nx;
+    if (lane_id() == 0) U[0] = (nx ? U[0] : 0u) ^ 1u;
+    wsync();
+    return nx > 1 ? nx : (rfl(U[0]) ? 1 : 0); // (one word, of any degree 0..31, unless it is now null)
+}
+
+// count_ones / count_zeros: E_j <- E_j + u_i E_{j-1} over the slots E_1 .. E_J, j descending so
+// that E_{j-1} is read before its own update; each product is formed in T (wave_mul's Dst may not
+// alias Add) and copied to its slot.  E_1 <- E_1 + u_i is an XOR in place.  Past slot J (n a power
+// of two) only the running product of all literals is still read: it goes on in D / Dn.
+__global__ void __launch_bounds__(256) bitcount_kernel(BitCountArgs G) {
+    extern __shared__ uint32_t lds[];
+    const CircuitIO &IO = G.io;
+    const uint32_t n = IO.nbits, J = G.J;
+    const WaveSlice ws = wave_slice(lds, G.lds_per_wave, IO.n);
+    if (!ws.live) return;
+    const int lane = lane_id();
+    uint32_t *L = ws.lds;
+    uint32_t *NE = L + G.oN, *U = L + G.oU, *T = L + G.oT, *E = L + G.oE; // NE[j]: words of E_j
+    uint32_t *D = L + G.oD, *Dn = D + G.cD;
+    for (uint32_t j = lane; j <= J; j += kWave) NE[j] = 0u;
+    wsync();
+    BitReader ra(IO.a, ws.e, IO.status);
+    int nd = 0, nout; // words of the running product in D
+    for (uint32_t i = 1; i <= n; ++i) {
+        const int nu = bitcount_literal(U, ra.load(i - 1, IO.ab.b[i - 1], U), G.zeros);
+        wsync();
+        if (G.diag && i > J) { // u_1 .. u_i from u_1 .. u_{i-1}: slot J's E_J^(J) at first
+            const uint32_t *P = i == J + 1 ? E + G.off[J] : D;
+            const int np = i == J + 1 ? (int)rfl(NE[J]) : nd;
+            nd = 0;
+            if (nu && np) {
+                nd = words_of(wave_mul<kQSmall, 8>(U, nu, P, np, nullptr, 0, Dn, &nout));
+                wsync();
+            }
+            uint32_t *x = D;
+            D = Dn, Dn = x;
+        }
+        if (!nu) continue; // a null literal changes no E_j
+        for (uint32_t j = min(i, J); j >= 2; --j) {
+            if (!bitcount_needed(n, i, j)) continue;
+            const int np = (int)rfl(NE[j - 1]);
+            if (!np) continue;
+            uint32_t *Ej = E + G.off[j];
+            const int ne = words_of(wave_mul<kQSmall, 8>(U, nu, E + G.off[j - 1], np, Ej,
+                                                         (int)rfl(NE[j]), T, &nout));
+            wsync();
+            wave_copy(T, ne, Ej);
+            if (lane == 0) NE[j] = (uint32_t)ne;
+            wsync();
+        }
+        uint32_t *E1 = E + G.off[1]; // E_1 <- E_1 + u_i E_0 (J >= 1)
+        const int ne = words_of(wave_xor(E1, (int)rfl(NE[1]), U, nu, E1));
+        if (lane == 0) NE[1] = (uint32_t)ne;
+        wsync();
+    }
+    BitWriter wo(IO.out, ws.e, IO.status);
+    for (uint32_t k = 0; k < kBitCountOut; ++k) {
+        const uint32_t t = 1u << k;
+        if (t <= J) wo.store(k, IO.ob.b[k], E + G.off[t], (int)rfl(NE[t]));
+        else if (G.diag && t == n) wo.store(k, IO.ob.b[k], D, nd);
+        else wo.store(k, IO.ob.b[k], nullptr, 0);
+    }
+}
+
+int launch_bitcount(const BitCountArgs &g, void *stream) {
+    return launch_wave_per_value(bitcount_kernel, g, g.io.n, g.lds_per_wave, stream);
+}
+
+// leading / trailing zeros / ones: the literals in the run's order, v_j = bit n - j (leading) or
+// j - 1 (trailing); t_j = t_{j-1} v_j in D / Dn, XORed into the accumulator of every output bit k
+// with 2^k | j.  Once t_j is null the chain stays null: the remaining bits are only loaded (their
+// degree words are validated like the others).
+__global__ void __launch_bounds__(256) bitrun_kernel(BitCountArgs G) {
+    extern __shared__ uint32_t lds[];
+    const CircuitIO &IO = G.io;
+    const uint32_t n = IO.nbits;
+    const WaveSlice ws = wave_slice(lds, G.lds_per_wave, IO.n);
+    if (!ws.live) return;
+    const int lane = lane_id();
+    uint32_t *L = ws.lds;
+    uint32_t *NA = L + G.oN, *U = L + G.oU, *A = L + G.oE; // NA[k]: words of accumulator k
+    uint32_t *D = L + G.oD, *Dn = D + G.cD;
+    if (lane < (int)kBitCountOut) NA[lane] = 0u;
+    wsync();
+    BitReader ra(IO.a, ws.e, IO.status);
+    if (G.leading) ra.off = G.a_limbs; // from the top bit down
+    int nt = 0, nout; // words of t_j in D
+    for (uint32_t j = 1; j <= n; ++j) {
+        const uint32_t i = G.leading ? n - j : j - 1;
+        const int nx = G.leading ? ra.load_down(i, IO.ab.b[i], U) : ra.load(i, IO.ab.b[i], U);
+        if (j > 1 && !nt) continue;
+        const int nu = bitcount_literal(U, nx, G.zeros);
+        wsync();
+        const int np = nt;
+        nt = 0;
+        if (j == 1) { // t_1 = v_1
+            wave_copy(U, nu, Dn);
+            nt = nu;
+        } else if (nu) {
+            nt = words_of(wave_mul<kQSmall, 8>(U, nu, D, np, nullptr, 0, Dn, &nout));
+        }
+        wsync();
+        uint32_t *x = D;
+        D = Dn, Dn = x;
+        if (!nt) continue;
+        for (uint32_t k = 0; k < G.K && !(j & ((1u << k) - 1u)); ++k) {
+            uint32_t *Ak = A + G.off[k];
+            const int na = words_of(wave_xor(Ak, (int)rfl(NA[k]), D, nt, Ak));
+            if (lane == 0) NA[k] = (uint32_t)na;
+        }
+        wsync();
+    }
+    BitWriter wo(IO.out, ws.e, IO.status);
+    for (uint32_t k = 0; k < kBitCountOut; ++k) {
+        if (k < G.K) wo.store(k, IO.ob.b[k], A + G.off[k], (int)rfl(NA[k]));
+        else wo.store(k, IO.ob.b[k], nullptr, 0);
+    }
+}
+
+int launch_bitrun(const BitCountArgs &g, void *stream) {
+    return launch_wave_per_value(bitrun_kernel, g, g.io.n, g.lds_per_wave, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

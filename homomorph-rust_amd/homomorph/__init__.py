@@ -34,12 +34,14 @@ __all__ = [
     "HomomorphicSelect", "HomomorphicMin", "HomomorphicMax", "HomomorphicLookup",
     "HomomorphicShiftLeft", "HomomorphicShiftRight", "HomomorphicRotateLeft",
     "HomomorphicRotateRight",
+    "HomomorphicCountOnes", "HomomorphicCountZeros", "HomomorphicLeadingZeros",
+    "HomomorphicLeadingOnes", "HomomorphicTrailingZeros", "HomomorphicTrailingOnes",
     "OperationError", "ContextCryptoError", "CipherError", "EngineError", "LibraryMissing",
     "EngineGraph",
     "add_out_bounds", "mul_out_bounds", "gate_out_bounds", "sub_out_bounds",
     "compare_out_bounds", "select_out_bounds", "minmax_out_bounds", "batch_stride", "caps",
     "select_into", "minmax_into", "lookup_out_bounds", "lookup_into",
-    "shift_out_bounds", "shift_into",
+    "shift_out_bounds", "shift_into", "bitcount_out_bounds", "bitcount_into",
 ]
 
 
@@ -223,6 +225,49 @@ class HomomorphicRotateLeft(_ShiftOp):
 
 class HomomorphicRotateRight(_ShiftOp):
     CODE = _lib.OP_ROTR
+
+
+class _BitCountOp(_WidthOp):
+    """A bit count of an encrypted value: ctx.bit_count(op, a), a Ciphered<u8>.
+    The width is that of the counted type, 1..128 bits.  A count (RUN False) is the elementary
+    symmetric polynomials e_{2^k} of the bits, m = 2^floor(log2 width); a run (RUN True) sums
+    prefix products of all the bits, m = width.  The requirement covers fresh operands."""
+    RUN = False
+
+    @classmethod
+    def min_d_over_delta(cls, nbits: int) -> int:
+        nbits = int(nbits)
+        if not 1 <= nbits <= _lib.HM_MAX_BITS:
+            raise ValueError("a counted type has 1..128 bits")
+        return 2 * (nbits if cls.RUN else 1 << (nbits.bit_length() - 1)) + 1
+
+
+class HomomorphicCountOnes(_BitCountOp):
+    CODE = _lib.OP_COUNT_ONES
+
+
+class HomomorphicCountZeros(_BitCountOp):
+    CODE = _lib.OP_COUNT_ZEROS
+
+
+class HomomorphicLeadingZeros(_BitCountOp):
+    CODE, RUN = _lib.OP_LEADING_ZEROS, True
+
+
+class HomomorphicLeadingOnes(_BitCountOp):
+    CODE, RUN = _lib.OP_LEADING_ONES, True
+
+
+class HomomorphicTrailingZeros(_BitCountOp):
+    CODE, RUN = _lib.OP_TRAILING_ZEROS, True
+
+
+class HomomorphicTrailingOnes(_BitCountOp):
+    CODE, RUN = _lib.OP_TRAILING_ONES, True
+
+
+def _is_bitcount(op) -> bool:
+    return isinstance(op, type) and issubclass(op, _BitCountOp)
 
 
 def _is_shift(op) -> bool:
@@ -425,6 +470,17 @@ def shift_out_bounds(op, a_bound, s_bound) -> np.ndarray:
     out = np.zeros_like(a)
     _check(lib().hm_shift_out_bounds(op.CODE, a.size, _p32(a), _p32(s), _p32(out)),
            "hm_shift_out_bounds")
+    return out
+
+
+def bitcount_out_bounds(op, a_bound) -> np.ndarray:
+    """hm_bitcount_out_bounds: the 8 per-bit bounds of bit_count(op, a) from a's bounds -- a
+    count's bit k the 2^k largest of them, a run's the first multiple of 2^k of them in the run's
+    order; 0 where 2^k exceeds the width."""
+    a = _u32(a_bound)
+    out = np.zeros(8, dtype=np.uint32)
+    _check(lib().hm_bitcount_out_bounds(getattr(op, "CODE", -1), a.size, _p32(a), _p32(out)),
+           "hm_bitcount_out_bounds")
     return out
 
 
@@ -853,8 +909,8 @@ class Context:
     def validate_operation(self, op, nbits=None) -> None:
         """Context::validate_operation (src/context.rs:310-323).  Built-in operations ask the
         engine (hm_validate_operation); a user operation supplies MIN_D_OVER_DELTA itself.
-        Subtraction, the comparisons, min / max, the shifts and the table lookup need a width
-        (nbits: of the type, for the lookup of the index): their requirement grows with it
+        Subtraction, the comparisons, min / max, the shifts, the bit counts and the table lookup
+        need a width (nbits: of the type, for the lookup of the index): their requirement grows with it
         (hm_validate_operation_bits)."""
         if not hasattr(op, "CODE"):
             req = int(op.MIN_D_OVER_DELTA)
@@ -964,6 +1020,20 @@ class Context:
         shift_into(self, op, a, amount, out, signed)
         return out
 
+    def bit_count(self, op, a: Ciphered, out_bound=None) -> Ciphered:
+        """a.count_ones(), count_zeros(), leading_zeros(), leading_ones(), trailing_zeros() or
+        trailing_ones() per value (hm_bitcount_batch); op is HomomorphicCountOnes ..
+        HomomorphicTrailingOnes.  a has any width in 1..128 bits (a value_slice of a wider type
+        counts that many bits).  The result is a batch of Ciphered<u8>: plain_dtype uint8."""
+        if not _is_bitcount(op):
+            raise ValueError("bit_count takes one of the six bit-count markers")
+        self.validate_operation(op, a.nbits)
+        need = bitcount_out_bounds(op, a.bound)
+        out = Ciphered.empty(a.n, need if out_bound is None else out_bound, self.device,
+                             np.dtype(np.uint8))
+        bitcount_into(self, op, a, out)
+        return out
+
     def mul_plan_work(self, a_bound, b_bound, k=None, signed=False) -> float:
         """hm_mul_plan_work: the carry products' word pairs as this context's plan runs them
         (Karatsuba products by their leaves) for the low k output bits (all when k is None)."""
@@ -992,7 +1062,11 @@ class Context:
     def apply1(self, op, a: Ciphered) -> Ciphered:
         """Context::apply1 (src/context.rs:496-510): validate, then HomomorphicOperation1::apply
         on `&mut a` -- IN PLACE, as the reference mutates its argument (the NOT gate keeps every
-        bound, so the kernel writes each bit over the one it read).  Returns `a` itself."""
+        bound, so the kernel writes each bit over the one it read).  Returns `a` itself.  The
+        bit-count markers are unary too but change the type: they return a new Ciphered<u8>
+        (bit_count)."""
+        if _is_bitcount(op):
+            return self.bit_count(op, a)
         self.validate_operation(op)
         need = gate_out_bounds(op, a.bound)
         if not np.array_equal(need, a.bound):
@@ -1117,6 +1191,13 @@ def shift_into(ctx: Context, op, a: Ciphered, amount: Ciphered, out: Ciphered, s
     ctx._launch(lambda: lib().hm_shift_batch(ctx._h, op.CODE, ctypes.byref(ca), ctypes.byref(cs),
                                              int(bool(signed)), ctypes.byref(co)),
                 "hm_shift_batch")
+
+
+def bitcount_into(ctx: Context, op, a: Ciphered, out: Ciphered) -> None:
+    """hm_bitcount_batch into a preallocated 8-bit output (bounds: bitcount_out_bounds)."""
+    ca, co = a._c(), out._c()
+    ctx._launch(lambda: lib().hm_bitcount_batch(ctx._h, op.CODE, ctypes.byref(ca),
+                                                ctypes.byref(co)), "hm_bitcount_batch")
 
 
 def minmax_into(ctx: Context, op, a: Ciphered, b: Ciphered, out: Ciphered, signed=None) -> None:

@@ -37,6 +37,8 @@ OP_SUB, OP_EQ, OP_NE, OP_LT, OP_LE, OP_GT, OP_GE = range(7, 14)
 OP_SELECT, OP_MIN, OP_MAX = range(14, 17)
 OP_LOOKUP = 17
 OP_SHL, OP_SHR, OP_ROTL, OP_ROTR = range(18, 22)
+(OP_COUNT_ONES, OP_COUNT_ZEROS, OP_LEADING_ZEROS, OP_LEADING_ONES, OP_TRAILING_ZEROS,
+ OP_TRAILING_ONES) = range(22, 28)
 
 u64p = ctypes.POINTER(ctypes.c_uint64)
 u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -122,6 +124,9 @@ SIGNATURES = {
     "hm_shift_batch": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(HmBatch),
                                       ctypes.POINTER(HmBatch), ctypes.c_int,
                                       ctypes.POINTER(HmBatch)]),
+    "hm_bitcount_out_bounds": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, u32p, u32p]),
+    "hm_bitcount_batch": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(HmBatch),
+                                         ctypes.POINTER(HmBatch)]),
     "hm_poly_add_batch": (ctypes.c_int, [vp] + [ctypes.POINTER(HmPolys)] * 3),
     "hm_poly_mul_batch": (ctypes.c_int, [vp] + [ctypes.POINTER(HmPolys)] * 3),
     "hm_poly_rem_batch": (ctypes.c_int, [vp, ctypes.POINTER(HmPolys), u64p, ctypes.c_size_t,

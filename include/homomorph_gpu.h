@@ -34,14 +34,16 @@
 extern "C" {
 #endif
 
-#define HM_ABI_VERSION 9 /* 4: kernel timing by device stamps (HM_TIME_*), hm_ctx_last_hip_error;
+#define HM_ABI_VERSION 10 /* 4: kernel timing by device stamps (HM_TIME_*), hm_ctx_last_hip_error;
                             5: hm_ctx_clear_kernel_timing, hm_ctx_set_mul_scratch;
                             6: HM_OP_SUB .. HM_OP_GE, hm_sub_batch, hm_compare_batch, their bounds,
                                hm_validate_operation_bits;
                             7: HM_OP_SELECT, HM_OP_MIN, HM_OP_MAX, hm_select_batch,
                                hm_minmax_batch, their bounds;
                             8: HM_OP_LOOKUP, hm_lookup_batch, hm_lookup_out_bounds;
-                            9: HM_OP_SHL .. HM_OP_ROTR, hm_shift_batch, hm_shift_out_bounds */
+                            9: HM_OP_SHL .. HM_OP_ROTR, hm_shift_batch, hm_shift_out_bounds;
+                            10: HM_OP_COUNT_ONES .. HM_OP_TRAILING_ONES, hm_bitcount_batch,
+                               hm_bitcount_out_bounds */
 #define HM_MAX_BITS 128 /* u128 is the widest type with impls (src/impls/numbers/uint.rs:58) */
 
 typedef enum hm_status {
@@ -118,6 +120,18 @@ typedef enum hm_op {
     HM_OP_SHR = 19,           /* HomomorphicShiftRight       a >> (s mod n), logical or arithmetic */
     HM_OP_ROTL = 20,          /* HomomorphicRotateLeft       a.rotate_left(s mod n) */
     HM_OP_ROTR = 21,          /* HomomorphicRotateRight      a.rotate_right(s mod n) */
+    /* Bit counts of an n-bit value, n in 1..128, as a Ciphered<u8> (hm_bitcount_batch), on the
+     * literals u_i = x_i (the "ones" ops) or x_i + 1 (the "zeros" ops).  A count's bit k is the
+     * elementary symmetric polynomial e_{2^k} of the literals, so m = 2^floor(log2 n); a run's
+     * bit k is a sum of prefix products of up to n literals, so m = n.  min d/delta = 2m + 1: for
+     * u8, u16, u32, u64 both kinds need 17, 33, 65, 129; at n = 24 a count needs 33 and a run 49.
+     * Width dependent (hm_validate_operation_bits), for fresh operands. */
+    HM_OP_COUNT_ONES = 22,     /* HomomorphicCountOnes        a.count_ones() */
+    HM_OP_COUNT_ZEROS = 23,    /* HomomorphicCountZeros       a.count_zeros() */
+    HM_OP_LEADING_ZEROS = 24,  /* HomomorphicLeadingZeros     a.leading_zeros() */
+    HM_OP_LEADING_ONES = 25,   /* HomomorphicLeadingOnes      a.leading_ones() */
+    HM_OP_TRAILING_ZEROS = 26, /* HomomorphicTrailingZeros    a.trailing_zeros() */
+    HM_OP_TRAILING_ONES = 27,  /* HomomorphicTrailingOnes     a.trailing_ones() */
 } hm_op;
 
 typedef struct hm_ctx hm_ctx;
@@ -274,9 +288,11 @@ hm_status hm_validate_operation(const hm_ctx *ctx, hm_op op, uint16_t *required_
  * HM_OP_LOOKUP: 2 nbits + 1 with nbits the index bits (hm_lookup_batch itself takes 1..8).
  * HM_OP_SHL .. HM_OP_ROTR: 2 log2(nbits) + 3 with nbits the width of the shifted type (u32: 13);
  * a width that is not a power of two in 2..HM_MAX_BITS is HM_ERR_INVALID_ARGUMENT.
+ * HM_OP_COUNT_ONES, HM_OP_COUNT_ZEROS: 2 * 2^floor(log2 nbits) + 1; HM_OP_LEADING_ZEROS ..
+ * HM_OP_TRAILING_ONES: 2 nbits + 1 (u32: 65 for both kinds; nbits = 24: 33 and 49).
  * HM_OP_SELECT has no width: both entries return 5.  hm_validate_operation itself has no width:
  * it returns HM_ERR_INVALID_ARGUMENT for HM_OP_SUB .. HM_OP_GE, HM_OP_MIN, HM_OP_MAX,
- * HM_OP_LOOKUP and HM_OP_SHL .. HM_OP_ROTR. */
+ * HM_OP_LOOKUP, HM_OP_SHL .. HM_OP_ROTR and HM_OP_COUNT_ONES .. HM_OP_TRAILING_ONES. */
 hm_status hm_validate_operation_bits(const hm_ctx *ctx, hm_op op, uint32_t nbits,
                                      uint16_t *required_min_d_over_delta);
 
@@ -356,6 +372,18 @@ hm_status hm_lookup_out_bounds(uint32_t in_bits, const uint32_t *a_bound, const 
  * is HM_ERR_UNSUPPORTED. */
 hm_status hm_shift_out_bounds(hm_op which, uint32_t nbits, const uint32_t *a_bound,
                               const uint32_t *s_bound, uint32_t *out_bound);
+/* Output bounds of hm_bitcount_batch(which, a), which = HM_OP_COUNT_ONES .. HM_OP_TRAILING_ONES
+ * (anything else is HM_ERR_INVALID_ARGUMENT) on nbits-bit values, nbits in 1..128 (anything else
+ * is HM_ERR_INVALID_ARGUMENT, as is a null pointer).  a_bound: nbits entries; writes the 8 bounds
+ * of a Ciphered<u8>.  Counts: out_bound[k] = the sum of the 2^k largest a_bound.  Runs: the sum of
+ * a_bound over the first M literals in the run's order (leading: from bit nbits - 1 down,
+ * trailing: from bit 0 up), M the largest multiple of 2^k that is <= nbits.  Bits with
+ * 2^k > nbits: 0 (null polynomials).  The zeros ops have the bounds of the ones ops.  (u32 at
+ * d + dp = 256: a count 256, 512, 1024, 2048, 4096, 8192, 0, 0, 260 limbs per value; a run 8192
+ * in bits 0..5, 776 limbs per value.)  A bound beyond the engine's degree range is
+ * HM_ERR_UNSUPPORTED. */
+hm_status hm_bitcount_out_bounds(hm_op which, uint32_t nbits, const uint32_t *a_bound,
+                                 uint32_t out_bound[8]);
 /* stride (limbs per value) of a batch with these bounds */
 uint64_t hm_batch_stride(uint32_t nbits, const uint32_t *bound);
 
@@ -476,6 +504,40 @@ hm_status hm_lookup_batch(hm_ctx *ctx, const hm_batch *a, uint32_t in_bits, cons
  * d + dp = 256, u64 at 512 and u32 at 1024 fit, u128 at d + dp = 512 does not). */
 hm_status hm_shift_batch(hm_ctx *ctx, hm_op which, const hm_batch *a, const hm_batch *amount,
                          int is_signed, hm_batch *out);
+
+/* a.count_ones(), count_zeros(), leading_zeros(), leading_ones(), trailing_zeros() or
+ * trailing_ones() per value, which = HM_OP_COUNT_ONES .. HM_OP_TRAILING_ONES (anything else is
+ * HM_ERR_INVALID_ARGUMENT), of n = a->nbits bits, n in 1..128 (any width: a 24-bit slice counts
+ * as 24 bits).  The result is a Ciphered<u8>.  With the literals u_i = x_i (ones) or x_i + 1
+ * (zeros: coefficient 0 flipped, so a unit polynomial becomes the null one):
+ *   counts  out_k = e_{2^k}(u_0 .. u_{n-1}), the elementary symmetric polynomial: at 0 / 1 values
+ *           it is C(c, 2^k) mod 2 for the count c, which is bit k of c (Lucas).  Evaluated by
+ *           E_j <- E_j + u_i E_{j-1} (j descending, E_0 = 1), literal after literal, skipping
+ *           every update no target 2^k <= n reads any more: 21, 85 and 341 products for u8, u16
+ *           and u32 (29, 101, 373 updates with those by E_0 = 1, which are XORs).
+ *   runs    with v_1 .. v_n the literals from the end counted (leading: v_j = u_{n-j}, trailing:
+ *           v_j = u_{j-1}) and t_j = v_1 .. v_j (the run is at least j),
+ *           out_k = sum of t_{m 2^k} over m >= 1, m 2^k <= n: n - 1 products, the sums are XORs.
+ * Every output bit is one fixed polynomial of the input bits whatever the order of evaluation:
+ * exact in GF(2)[X] (for a byte, the polynomials hm_lookup_batch gives for the same function's
+ * table).  Output bits with 2^k > n are null polynomials.  out: out->nbits == 8, out->n == a->n,
+ * bounds from hm_bitcount_out_bounds (larger ones are accepted, smaller ones
+ * HM_ERR_INVALID_ARGUMENT); out may not overlap a, in limbs or in degree words
+ * (HM_ERR_INVALID_ARGUMENT).  Every bit of a is read and validated.  Validates which at a->nbits:
+ * the requirement covers fresh operands; operands that came out of another operation carry that
+ * operation's depth, which the caller accounts for.  One launch, no workspace: a count keeps
+ * E_1 .. E_J at their bounds in LDS (J = n / 2 for a power of two, whose top target e_n is the
+ * running product of all literals, else 2^floor(log2 n)), a run its prefix and one accumulator
+ * per output bit; HM_ERR_UNSUPPORTED (before any launch) when that does not fit a wavefront's
+ * share of LDS, here 2560 words: a quarter of the other circuits' share, so that four blocks stay
+ * resident on a compute unit.  At one bound D = d + dp on every bit, words per wave (-: refused):
+ *              u8 D=128/256/512   u16 D=128/256/512   u32 D=128/256/512   u64 D=64/128/256
+ *   counts     148 / 272 / 520    344 / 652 / 1268    928 / 1796 / -      1486 / - / -
+ *   runs       220 / 416 / 808    478 / 930 / 1834    1056 / 2084 / -     1184 / 2338 / -
+ * so every op runs u8 and u16 up to D = 512 and u32 up to D = 256 (the headline parameters);
+ * u32 at D = 512 and u64 at D = 256 do not fit (a u64 count at 256 would keep E_1 .. E_32, 4288
+ * words), and u128 runs up to D = 32 (a count up to D = 16). */
+hm_status hm_bitcount_batch(hm_ctx *ctx, hm_op which, const hm_batch *a, hm_batch *out);
 
 /* ---------------- polynomial primitives (src/polynomial.rs), for unit parity ---------------- */
 /* Polynomial::add (polynomial.rs:190-213) per pair: out = a ^ b, exact degree. */
