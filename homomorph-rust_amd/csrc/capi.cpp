@@ -5,7 +5,8 @@
 // 310-323; Parameters::new asserts, :87-94) and launches the kernels.  The static degree bounds
 // and the plans come from host-only headers: the adder's from add_host.h (plan_add), the
 // wave-per-value circuits' from circuit_host.h (plan_gate, plan_borrow, plan_select),
-// lookup_host.h (plan_lookup), shift_host.h (plan_shift) and bitcount_host.h (plan_bitcount); the
+// lookup_host.h (plan_lookup), shift_host.h (plan_shift), bitcount_host.h (plan_bitcount) and
+// array_host.h (plan_array_read, plan_array_write); the
 // multiplier's from mul_host.cpp.
 // Never throws across the ABI.
 #include <hip/hip_runtime.h>
@@ -21,6 +22,7 @@
 #include <sys/random.h>
 
 #include "add_host.h"
+#include "array_host.h"
 #include "bitcount_host.h"
 #include "circuit_host.h"
 #include "ctx.h"
@@ -125,9 +127,10 @@ bool is_ordering_op(hm_op op) { return op >= HM_OP_LT && op <= HM_OP_GE; }
 bool is_minmax_op(hm_op op) { return op == HM_OP_MIN || op == HM_OP_MAX; }
 using shift_plan::is_shift_op;
 using bitcount_plan::is_bitcount_op;
+using array_plan::is_array_op;
 bool needs_width(hm_op op) {
     return is_borrow_op(op) || is_minmax_op(op) || op == HM_OP_LOOKUP || is_shift_op(op) ||
-           is_bitcount_op(op);
+           is_bitcount_op(op) || is_array_op(op);
 }
 
 // 2m + 1 with m the borrow circuit's degree in fresh input bits: nbits + 1 for the orderings
@@ -136,11 +139,14 @@ bool needs_width(hm_op op) {
 // A shift or rotate of an nbits-bit value is log2 nbits selects deep: m = log2 nbits + 1 (the
 // caller has checked the width, shift_plan::stages).  A bit count's m is bitcount_plan::degree_of:
 // the top symmetric polynomial 2^floor(log2 nbits) of a count, the whole prefix nbits of a run.
+// An array read or write by nbits index bits multiplies an indicator of nbits literals by one
+// more bit: m = nbits + 1 (array_plan::degree_of).
 // A fresh bit's noise has degree delta + 1 <= 2 delta, so d >= (2m + 1) delta gives
 // m (delta + 1) < d.
 uint16_t borrow_min_d_over_delta(hm_op op, uint32_t nbits) {
     if (is_shift_op(op)) return (uint16_t)(2 * shift_plan::stages(nbits) + 3);
     if (is_bitcount_op(op)) return (uint16_t)(2 * bitcount_plan::degree_of(op, nbits) + 1);
+    if (is_array_op(op)) return (uint16_t)(2 * array_plan::degree_of(nbits) + 1);
     const uint32_t m = nbits + (is_ordering_op(op) ? 1u : is_minmax_op(op) ? 2u : 0u);
     return (uint16_t)(2 * m + 1);
 }
@@ -662,6 +668,7 @@ hm_status hm_validate_operation_bits(const hm_ctx *c, hm_op op, uint32_t nbits, 
     if (!needs_width(op)) return hm_validate_operation(c, op, req);
     if (!c || nbits == 0 || nbits > HM_MAX_BITS) return HM_ERR_INVALID_ARGUMENT;
     if (is_shift_op(op) && !shift_plan::stages(nbits)) return HM_ERR_INVALID_ARGUMENT;
+    if (is_array_op(op) && nbits > kArrayMaxIndex) return HM_ERR_INVALID_ARGUMENT; // index bits
     const uint16_t m = borrow_min_d_over_delta(op, nbits);
     if (req) *req = m;
     if ((uint32_t)c->d < (uint32_t)m * (uint32_t)c->delta) return HM_ERR_INVALID_PARAMETERS;
@@ -748,6 +755,22 @@ hm_status hm_bitcount_out_bounds(hm_op which, uint32_t nbits, const uint32_t *a,
     if (!a || !out || !is_bitcount_op(which) || nbits == 0 || nbits > HM_MAX_BITS)
         return HM_ERR_INVALID_ARGUMENT;
     return bitcount_plan::bounds(which, nbits, a, out);
+} HM_ABI_CATCH
+
+// Degree bounds of an array read or write by an encrypted index.
+hm_status hm_array_read_out_bounds(uint32_t nbits, const uint32_t *arr, uint32_t count,
+                                   const uint32_t *s, uint32_t *out) try {
+    if (!arr || !s || !out || nbits == 0 || nbits > HM_MAX_BITS || !array_plan::index_bits(count))
+        return HM_ERR_INVALID_ARGUMENT;
+    return array_plan::read_bounds(nbits, arr, count, s, out);
+} HM_ABI_CATCH
+
+hm_status hm_array_write_out_bounds(uint32_t nbits, const uint32_t *arr, const uint32_t *x,
+                                    uint32_t count, const uint32_t *s, uint32_t *out) try {
+    if (!arr || !x || !s || !out || nbits == 0 || nbits > HM_MAX_BITS ||
+        !array_plan::index_bits(count))
+        return HM_ERR_INVALID_ARGUMENT;
+    return array_plan::write_bounds(nbits, arr, x, count, s, out);
 } HM_ABI_CATCH
 
 hm_status hm_minmax_out_bounds(uint32_t L, const uint32_t *a, const uint32_t *b,
@@ -1122,6 +1145,75 @@ hm_status hm_bitcount_batch(hm_ctx *c, hm_op which, const hm_batch *a, hm_batch 
     if (hm_status st = plan_bitcount(which, a->nbits, a->bound, G); st) return st;
     fill_io(G.io, c, a, nullptr, out);
     return run_circuit(c, G, bitcount_plan::is_run_op(which) ? launch_bitrun : launch_bitcount);
+} HM_ABI_CATCH
+
+// What the two array entries check of their batches (check_operands assumes one n and one width):
+// each batch on its own, the index's k bits, the elements' width on out (and value), and the value
+// counts: n indices, count n elements (or, a shared table, count).
+static hm_status check_array(const hm_batch *arr, uint32_t count, const hm_batch *index,
+                             const hm_batch *value, const hm_batch *out, uint32_t *k) {
+    for (const hm_batch *x : {arr, index, out})
+        if (hm_status st = check_batch(x); st) return st;
+    if (value)
+        if (hm_status st = check_batch(value); st) return st;
+    *k = array_plan::index_bits(count);
+    if (!*k || index->nbits < *k || out->nbits != arr->nbits) return HM_ERR_INVALID_ARGUMENT;
+    const uint64_t n = index->n;
+    if (value) { // write: no shared form
+        if (value->nbits != arr->nbits || value->n != n || arr->n != count * n || out->n != arr->n)
+            return HM_ERR_INVALID_ARGUMENT;
+    } else if (out->n != n || (arr->n != count * n && arr->n != count)) {
+        return HM_ERR_INVALID_ARGUMENT;
+    }
+    return HM_OK;
+}
+
+hm_status hm_array_read_batch(hm_ctx *c, const hm_batch *arr, uint32_t count,
+                              const hm_batch *index, hm_batch *out) try {
+    if (!c || !arr || !index || !out) return HM_ERR_INVALID_ARGUMENT;
+    uint32_t k;
+    if (hm_status st = check_array(arr, count, index, nullptr, out, &k); st) return st;
+    if (hm_status st = hm_validate_operation_bits(c, HM_OP_ARRAY_READ, k, nullptr); st) return st;
+    std::vector<uint32_t> need(arr->nbits);
+    if (hm_status st = array_plan::read_bounds(arr->nbits, arr->bound, count, index->bound,
+                                               need.data());
+        st)
+        return st;
+    if (!covers(out, need) || overlaps(out, arr) || overlaps(out, index))
+        return HM_ERR_INVALID_ARGUMENT;
+    if (index->n == 0) return HM_OK;
+    ArrayReadArgs G{};
+    const bool shared = arr->n != count * index->n; // (n = 1: the two forms are one)
+    if (hm_status st = plan_array_read(arr->nbits, arr->bound, count, index->bound, shared, G); st)
+        return st;
+    fill_io(G.io, c, arr, index, out);
+    G.io.n = index->n;
+    return run_circuit(c, G, launch_array_read);
+} HM_ABI_CATCH
+
+hm_status hm_array_write_batch(hm_ctx *c, const hm_batch *arr, uint32_t count,
+                               const hm_batch *index, const hm_batch *value, hm_batch *out) try {
+    if (!c || !arr || !index || !value || !out) return HM_ERR_INVALID_ARGUMENT;
+    uint32_t k;
+    if (hm_status st = check_array(arr, count, index, value, out, &k); st) return st;
+    if (hm_status st = hm_validate_operation_bits(c, HM_OP_ARRAY_WRITE, k, nullptr); st) return st;
+    std::vector<uint32_t> need(arr->nbits);
+    if (hm_status st = array_plan::write_bounds(arr->nbits, arr->bound, value->bound, count,
+                                                index->bound, need.data());
+        st)
+        return st;
+    if (!covers(out, need) || overlaps(out, arr) || overlaps(out, index) || overlaps(out, value))
+        return HM_ERR_INVALID_ARGUMENT;
+    if (index->n == 0) return HM_OK;
+    ArrayWriteArgs G{};
+    if (hm_status st = plan_array_write(arr->nbits, arr->bound, value->bound, count, index->bound,
+                                        G);
+        st)
+        return st;
+    fill_io(G.io, c, arr, value, out);
+    G.io.n = index->n;
+    G.idx = batch_arg(index);
+    return run_circuit(c, G, launch_array_write);
 } HM_ABI_CATCH
 
 // ------------------------------------------------------------------ polynomial primitives

@@ -114,7 +114,7 @@ struct DecArgs {
 // The wave-per-value circuits (kernels.hip: gates, borrow chain, min / max, select, lookup, shift,
 // bit counts) keep their intermediates in LDS, one wavefront per value, in a slice of lds_per_wave
 // words whose layout the host plans (circuit_host.h, lookup_host.h, shift_host.h,
-// bitcount_host.h).  What their argument
+// bitcount_host.h, array_host.h).  What their argument
 // blocks share, filled by capi.cpp fill_io: the operands, the output and their static bounds.
 struct CircuitIO {
     BatchArg a, b, out; // b: the second operand (a shift's amount; a unary gate has none)
@@ -277,9 +277,48 @@ struct BitCountArgs {
     uint32_t off[kBitCountMaxSlots + 1];
     CircuitIO io;
 };
+// Oblivious array read and write by an encrypted index (kernels.hip array_read_kernel and
+// array_write_kernel), one wavefront per index value.  An array of count
+// elements is count consecutive values of an ordinary batch: element v of array e is value
+// e count + v (a shared table: value v).  k = ceil(log2 count) index bits s_0 .. s_{k-1} are read.
+//   read   out_j = sum_v ind_v T_{v,j} as a multiplexer tree, one output bit at a time: the
+//          elements are walked in order, a level-t node (2^t elements) either parks in slot t as
+//          a waiting left child or is joined with the parked one, y = L + s_t (L + R), and rises.
+//          A right sibling past the array is the null polynomial.
+//   write  out_{v,j} = T_{v,j} + ind_v (x_j + T_{v,j}), ind_v = prod_t (s_t or s_t + 1) kept as
+//          the suffix products Q_t = prod_{i >= t} lit_i(v) in k slots: stepping v recomputes
+//          only the levels at or below its lowest set bit.  x's bits stay in LDS for the value.
+// Everything below but io is filled by array_host.h plan_array_read / plan_array_write.  The slot
+// offsets and bounds travel by value: every index into them is wave-uniform (dev_common.h).
+constexpr uint32_t kArrayMaxIndex = 8;   // index bits
+constexpr uint32_t kArrayMaxCount = 256; // elements
+struct ArrayReadArgs {
+    uint32_t count, k;
+    uint32_t shared;    // arr holds one table of count values, read by every index
+    // word offsets in a wave's LDS slice: word counts (8 of the index bits, 8 of the slots) | the
+    // index bits at soff[t] | an odd element's bit | L + R | two ping-pong product buffers of cP
+    // words each | the waiting left children, level t at slot[t]
+    uint32_t lds_per_wave, oN, oL, oX, oP, cP;
+    uint32_t soff[kArrayMaxIndex];
+    uint32_t slot[kArrayMaxIndex];
+    CircuitIO io;       // a: the array batch, b: the index (its low k bits), n: index values
+};
+struct ArrayWriteArgs {
+    uint32_t count, k;
+    // word offsets in a wave's LDS slice: word counts (8 of the index bits, 8 of the suffix
+    // products, nbits of x's bits) | the index bits at soff[t] | the literal | the element's bit |
+    // x_j + T_j | the product | the suffix products at qoff[t] | x's bits, whole limbs, at oV
+    uint32_t lds_per_wave, oN, oU, oT, oX, oO, oV;
+    uint32_t soff[kArrayMaxIndex];
+    uint32_t qoff[kArrayMaxIndex];
+    uint32_t sb[kArrayMaxIndex]; // the index bits' bounds
+    BatchArg idx;                // the index (its low k bits)
+    CircuitIO io;                // a: the array batch, b: the value written, n: index values
+};
 static_assert(sizeof(ShiftArgs) < 4096 && sizeof(LookupArgs) < 4096 && sizeof(SelectArgs) < 4096 &&
                   sizeof(BorrowArgs) < 4096 && sizeof(MinMaxArgs) < 4096 && sizeof(GateArgs) < 4096 &&
-                  sizeof(BitCountArgs) < 4096,
+                  sizeof(BitCountArgs) < 4096 && sizeof(ArrayReadArgs) < 4096 &&
+                  sizeof(ArrayWriteArgs) < 4096,
               "kernarg limit");
 
 // Column-parallel carry-save multiplier (mul_engine.hip, mul_host.cpp).  Column i of
@@ -568,6 +607,8 @@ int launch_lookup(const LookupArgs &a, void *stream);
 int launch_shift(const ShiftArgs &a, void *stream);
 int launch_bitcount(const BitCountArgs &a, void *stream); // count_ones, count_zeros
 int launch_bitrun(const BitCountArgs &a, void *stream);   // leading / trailing zeros / ones
+int launch_array_read(const ArrayReadArgs &a, void *stream);
+int launch_array_write(const ArrayWriteArgs &a, void *stream);
 int launch_mul_stage(const MulStageArgs &a, void *stream);
 int launch_mul_pp(const MulPPArgs &a, void *stream);
 int launch_mul_scan(const MulScanArgs &a, void *stream);

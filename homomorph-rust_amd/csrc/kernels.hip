@@ -8,6 +8,7 @@
 //   lookup_kernel   T[v] for a plaintext table T and an encrypted index of up to 8 bits (s4.4c)
 //   shift_kernel    <<, >>, rotates by an encrypted amount: a barrel shifter in LDS (s4.4d)
 //   bitcount_kernel, bitrun_kernel   count_ones / count_zeros; leading / trailing runs (s4.4e)
+//   array_read_kernel, array_write_kernel   arr[i] and arr[i] = x for an encrypted index (s4.4f)
 //   poly_* kernels single-polynomial primitives for unit parity (polynomial.rs:190-365)
 // (adder: adder.hip; cipher: cipher.hip; carry-save multiplier: mul_engine.hip)
 #include <hip/hip_runtime.h>
@@ -17,7 +18,7 @@
 namespace hm {
 
 // The launch of the wave-per-value circuits (gates, borrow chain, min / max, select, lookup,
-// shift, bit counts): one wavefront per value, 4 per block, lds_per_wave words of dynamic LDS each.
+// shift, bit counts, array read / write): one wavefront per value, 4 per block, lds_per_wave words of dynamic LDS each.
 template <class Args>
 static int launch_wave_per_value(void (*kernel)(Args), const Args &g, uint64_t n,
                                  uint32_t lds_per_wave, void *stream) {
@@ -551,6 +552,169 @@ __global__ void __launch_bounds__(256) bitrun_kernel(BitCountArgs G) {
 
 int launch_bitrun(const BitCountArgs &g, void *stream) {
     return launch_wave_per_value(bitrun_kernel, g, g.io.n, g.lds_per_wave, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Oblivious array read and write by an encrypted index (ArrayReadArgs / ArrayWriteArgs, DESIGN.md
+// s4.4f).  One wavefront per index value; element v of its array is value e count + v of the array
+// batch (64-bit arithmetic), or value v of a shared table.  The short operand of every product is
+// the uniform one; a null factor skips its product on a scalar branch.
+
+// read: one output bit at a time, the elements in order through a stack of one waiting left child
+// per tree level.  A level-t node (an even element's bit is loaded straight into slot 0) parks in
+// slot t when bit t of v is 0, or is joined with the one parked there, y = L + s_t (L + R): L + R
+// into X, the product into the ping-pong buffer the node is not in.  Under the last element a
+// node with nothing parked beside it has the null polynomial for its right sibling, y = L + s_t L,
+// and goes on rising: the walk ends at the root, level k.  A skipped product leaves the node
+// where its L is (a slot; it is copied only when it parks).
+__global__ void __launch_bounds__(256) array_read_kernel(ArrayReadArgs G) {
+    extern __shared__ uint32_t lds[];
+    const CircuitIO &IO = G.io;
+    const uint32_t k = G.k, count = G.count;
+    const WaveSlice ws = wave_slice(lds, G.lds_per_wave, IO.n);
+    if (!ws.live) return;
+    const int lane = lane_id();
+    uint32_t *L = ws.lds;
+    uint32_t *NS = L + G.oN, *NK = NS + kArrayMaxIndex; // word counts: index bits, slots
+    uint32_t *Ld = L + G.oL, *X = L + G.oX, *P0 = L + G.oP, *P1 = P0 + G.cP;
+    BitReader rs(IO.b, ws.e, IO.status);
+    for (uint32_t t = 0; t < k; ++t) {
+        const int ns = rs.load(t, IO.bb.b[t], L + G.soff[t]);
+        if (lane == 0) NS[t] = (uint32_t)ns;
+    }
+    wsync();
+    const uint64_t first = G.shared ? 0ull : ws.e * count;
+    BitWriter wo(IO.out, ws.e, IO.status);
+    uint32_t aoff = 0; // limbs of an element before bit j
+    for (uint32_t j = 0; j < IO.nbits; ++j) {
+        const uint32_t bj = IO.ab.b[j];
+        for (uint32_t v = 0; v < count; ++v) {
+            BitReader ra(IO.a, first + v, IO.status);
+            ra.off = aoff;
+            uint32_t *node = v & 1u ? Ld : L + G.slot[0];
+            int nn = ra.load(j, bj, node);
+            wsync();
+            uint32_t t = 0;
+            for (; t < k; ++t) {
+                uint32_t *Sl = L + G.slot[t];
+                const uint32_t *V, *Add; // the product's long factor, and what it is added to
+                int nv, nadd;
+                if ((v >> t) & 1u) { // joins the left child parked at this level
+                    nadd = (int)rfl(NK[t]);
+                    nv = words_of(wave_xor(Sl, nadd, node, nn, X));
+                    wsync();
+                    V = X, Add = Sl;
+                } else if (v + 1 == count) { // the right sibling is past the array: null
+                    V = Add = node, nv = nadd = nn;
+                } else { // waits for its right sibling
+                    if (node != Sl) wave_copy(node, nn, Sl);
+                    if (lane == 0) NK[t] = (uint32_t)nn;
+                    wsync();
+                    break;
+                }
+                const int ns = (int)rfl(NS[t]);
+                if (ns && nv) {
+                    uint32_t *Dst = node == P0 ? P1 : P0;
+                    int nout;
+                    nn = words_of(wave_mul<kQSmall, 8>(L + G.soff[t], ns, V, nv, Add, nadd, Dst,
+                                                       &nout));
+                    wsync();
+                    node = Dst;
+                } else {
+                    node = const_cast<uint32_t *>(Add), nn = nadd;
+                }
+            }
+            if (t == k) { // (the last element only) the root
+                wo.store(j, IO.ob.b[j], node, nn);
+                wsync();
+            }
+        }
+        aoff += cap_of(bj);
+    }
+}
+
+int launch_array_read(const ArrayReadArgs &g, void *stream) {
+    return launch_wave_per_value(array_read_kernel, g, g.io.n, g.lds_per_wave, stream);
+}
+
+// write: the suffix products Q_t = prod_{i >= t} lit_i(v) in k slots, Q_0 the indicator of v.
+// From v - 1 to v the bits up to v's lowest set bit change: those levels are formed again from the
+// top one down (level k - 1 is the literal itself), the literal s_t + 1 of a 0 bit as
+// bitcount_literal forms it from a copy of s_t.  Then out_j = T_j + Q_0 (x_j + T_j) for every bit
+// of element v, x's bits held in LDS since the start; a null Q_0 or x_j + T_j stores T_j itself.
+__global__ void __launch_bounds__(256) array_write_kernel(ArrayWriteArgs G) {
+    extern __shared__ uint32_t lds[];
+    const CircuitIO &IO = G.io;
+    const uint32_t k = G.k, count = G.count;
+    const WaveSlice ws = wave_slice(lds, G.lds_per_wave, IO.n);
+    if (!ws.live) return;
+    const int lane = lane_id();
+    uint32_t *L = ws.lds;
+    // word counts: index bits, suffix products, x's bits
+    uint32_t *NS = L + G.oN, *NQ = NS + kArrayMaxIndex, *NX = NQ + kArrayMaxIndex;
+    uint32_t *U = L + G.oU, *T = L + G.oT, *X = L + G.oX, *O = L + G.oO, *XV = L + G.oV;
+    BitReader rs(G.idx, ws.e, IO.status), rx(IO.b, ws.e, IO.status);
+    for (uint32_t t = 0; t < k; ++t) {
+        const int ns = rs.load(t, G.sb[t], L + G.soff[t]);
+        if (lane == 0) NS[t] = (uint32_t)ns;
+    }
+    uint32_t xo = 0;
+    for (uint32_t j = 0; j < IO.nbits; ++j) {
+        const int nx = rx.load(j, IO.bb.b[j], XV + xo);
+        if (lane == 0) NX[j] = (uint32_t)nx;
+        xo += 2 * cap_of(IO.bb.b[j]);
+    }
+    wsync();
+    for (uint32_t v = 0; v < count; ++v) {
+        for (int t = v ? __builtin_ctz(v) : (int)k - 1; t >= 0; --t) {
+            const int ns = (int)rfl(NS[t]);
+            wave_copy(L + G.soff[t], ns, U);
+            wsync();
+            const int nu = bitcount_literal(U, ns, !((v >> t) & 1u));
+            wsync();
+            uint32_t *Q = L + G.qoff[t];
+            int nq = 0, nout;
+            if (t == (int)k - 1) {
+                wave_copy(U, nu, Q);
+                nq = nu;
+            } else {
+                const int np = (int)rfl(NQ[t + 1]);
+                if (nu && np)
+                    nq = words_of(wave_mul<kQSmall, 8>(U, nu, L + G.qoff[t + 1], np, nullptr, 0, Q,
+                                                       &nout));
+            }
+            if (lane == 0) NQ[t] = (uint32_t)nq;
+            wsync();
+        }
+        const uint32_t *Q0 = L + G.qoff[0];
+        const int nind = (int)rfl(NQ[0]);
+        const uint64_t el = ws.e * count + v;
+        BitReader ra(IO.a, el, IO.status);
+        BitWriter wo(IO.out, el, IO.status);
+        xo = 0;
+        for (uint32_t j = 0; j < IO.nbits; ++j) {
+            const int nt = ra.load(j, IO.ab.b[j], T);
+            wsync();
+            int nx = 0, nout;
+            if (nind) {
+                nx = words_of(wave_xor(XV + xo, (int)rfl(NX[j]), T, nt, X));
+                wsync();
+            }
+            if (nx) {
+                const int no = words_of(wave_mul<kQSmall, 8>(X, nx, Q0, nind, T, nt, O, &nout));
+                wsync();
+                wo.store(j, IO.ob.b[j], O, no);
+            } else {
+                wo.store(j, IO.ob.b[j], T, nt);
+            }
+            wsync();
+            xo += 2 * cap_of(IO.bb.b[j]);
+        }
+    }
+}
+
+int launch_array_write(const ArrayWriteArgs &g, void *stream) {
+    return launch_wave_per_value(array_write_kernel, g, g.io.n, g.lds_per_wave, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

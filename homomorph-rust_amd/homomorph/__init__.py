@@ -36,12 +36,15 @@ __all__ = [
     "HomomorphicRotateRight",
     "HomomorphicCountOnes", "HomomorphicCountZeros", "HomomorphicLeadingZeros",
     "HomomorphicLeadingOnes", "HomomorphicTrailingZeros", "HomomorphicTrailingOnes",
+    "HomomorphicArrayRead", "HomomorphicArrayWrite",
     "OperationError", "ContextCryptoError", "CipherError", "EngineError", "LibraryMissing",
     "EngineGraph",
     "add_out_bounds", "mul_out_bounds", "gate_out_bounds", "sub_out_bounds",
     "compare_out_bounds", "select_out_bounds", "minmax_out_bounds", "batch_stride", "caps",
     "select_into", "minmax_into", "lookup_out_bounds", "lookup_into",
     "shift_out_bounds", "shift_into", "bitcount_out_bounds", "bitcount_into",
+    "array_read_out_bounds", "array_write_out_bounds", "array_read_into", "array_write_into",
+    "stack_values",
 ]
 
 
@@ -266,8 +269,60 @@ class HomomorphicTrailingOnes(_BitCountOp):
     CODE, RUN = _lib.OP_TRAILING_ONES, True
 
 
+class _ArrayOp(_WidthOp):
+    """An array read or write by an encrypted index: ctx.array_read(arr, index, count),
+    ctx.array_write(arr, index, value, count).  The width is the number of index
+    bits k = ceil(log2 count), 1..8 (index_bits(count)); an indicator of k literals times one more
+    bit, so m = k + 1.  The requirement covers fresh operands."""
+
+    @classmethod
+    def min_d_over_delta(cls, nbits: int) -> int:
+        nbits = int(nbits)
+        if not 1 <= nbits <= 8:
+            raise ValueError("an array is indexed by 1..8 bits")
+        return 2 * nbits + 3
+
+    @staticmethod
+    def index_bits(count: int) -> int:
+        count = int(count)
+        if not 2 <= count <= 256:
+            raise ValueError("an array has 2..256 elements")
+        return (count - 1).bit_length()
+
+
+class HomomorphicArrayRead(_ArrayOp):
+    """arr[index]: ctx.apply_n(HomomorphicArrayRead, [arr, index]) infers count = arr.n // index.n
+    (arrays per value); ctx.array_read also takes one shared table."""
+    CODE = _lib.OP_ARRAY_READ
+
+    @classmethod
+    def apply(cls, ctx: "Context", args) -> "Ciphered":
+        arr, index = args
+        return ctx.array_read(arr, index, _array_count(arr, index))
+
+
+class HomomorphicArrayWrite(_ArrayOp):
+    """arr with arr[index] = value: ctx.apply_n(HomomorphicArrayWrite, [arr, index, value])."""
+    CODE = _lib.OP_ARRAY_WRITE
+
+    @classmethod
+    def apply(cls, ctx: "Context", args) -> "Ciphered":
+        arr, index, value = args
+        return ctx.array_write(arr, index, value, _array_count(arr, index))
+
+
+def _array_count(arr, index) -> int:
+    if index.n == 0 or arr.n % index.n:
+        raise ValueError("an array batch holds count elements per index value")
+    return arr.n // index.n
+
+
 def _is_bitcount(op) -> bool:
     return isinstance(op, type) and issubclass(op, _BitCountOp)
+
+
+def _is_array(op) -> bool:
+    return isinstance(op, type) and issubclass(op, _ArrayOp)
 
 
 def _is_shift(op) -> bool:
@@ -481,6 +536,37 @@ def bitcount_out_bounds(op, a_bound) -> np.ndarray:
     out = np.zeros(8, dtype=np.uint32)
     _check(lib().hm_bitcount_out_bounds(getattr(op, "CODE", -1), a.size, _p32(a), _p32(out)),
            "hm_bitcount_out_bounds")
+    return out
+
+
+def _index_bounds(count, s_bound):
+    k = _ArrayOp.index_bits(count)
+    s = _u32(s_bound)
+    if s.size < k:
+        raise ValueError(f"an array of {count} reads {k} index bits: as many bounds")
+    return np.ascontiguousarray(s[:k])
+
+
+def array_read_out_bounds(arr_bound, count, s_bound) -> np.ndarray:
+    """hm_array_read_out_bounds: per-bit bounds of array_read(arr, index, count) from the
+    elements' bounds and the bounds of the index's low ceil(log2 count) bits (more may be given:
+    the rest is not read)."""
+    a, s = _u32(arr_bound), _index_bounds(count, s_bound)
+    out = np.zeros_like(a)
+    _check(lib().hm_array_read_out_bounds(a.size, _p32(a), int(count), _p32(s), _p32(out)),
+           "hm_array_read_out_bounds")
+    return out
+
+
+def array_write_out_bounds(arr_bound, x_bound, count, s_bound) -> np.ndarray:
+    """hm_array_write_out_bounds: per-bit bounds, shared by all elements, of
+    array_write(arr, index, value, count)."""
+    a, x, s = _u32(arr_bound), _u32(x_bound), _index_bounds(count, s_bound)
+    if x.size != a.size:
+        raise ValueError("the value written has the elements' width")
+    out = np.zeros_like(a)
+    _check(lib().hm_array_write_out_bounds(a.size, _p32(a), _p32(x), int(count), _p32(s),
+                                           _p32(out)), "hm_array_write_out_bounds")
     return out
 
 
@@ -909,8 +995,9 @@ class Context:
     def validate_operation(self, op, nbits=None) -> None:
         """Context::validate_operation (src/context.rs:310-323).  Built-in operations ask the
         engine (hm_validate_operation); a user operation supplies MIN_D_OVER_DELTA itself.
-        Subtraction, the comparisons, min / max, the shifts, the bit counts and the table lookup
-        need a width (nbits: of the type, for the lookup of the index): their requirement grows with it
+        Subtraction, the comparisons, min / max, the shifts, the bit counts, the table lookup and
+        the array read and write need a width (nbits: of the type, for the lookup and the arrays
+        of the index): their requirement grows with it
         (hm_validate_operation_bits)."""
         if not hasattr(op, "CODE"):
             req = int(op.MIN_D_OVER_DELTA)
@@ -1034,6 +1121,31 @@ class Context:
         bitcount_into(self, op, a, out)
         return out
 
+    def array_read(self, arr: Ciphered, index: Ciphered, count: int, out_bound=None) -> Ciphered:
+        """arr[i] per value for an ENCRYPTED index (hm_array_read_batch).  arr is an array batch:
+        count consecutive values per array (ctx.encrypt of a flat (n * count,) array, or
+        stack_values), arr.n == count * index.n; or arr.n == count: one shared table read by every
+        index.  count is any integer in 2..256; only the index's low ceil(log2 count) ciphertext
+        bits are read, and an index >= count reads 0.  The output keeps arr's plaintext dtype."""
+        self.validate_operation(HomomorphicArrayRead, _ArrayOp.index_bits(count))
+        need = array_read_out_bounds(arr.bound, count, index.bound)
+        out = Ciphered.empty(index.n, need if out_bound is None else out_bound, self.device,
+                             arr.plain_dtype)
+        array_read_into(self, arr, index, count, out)
+        return out
+
+    def array_write(self, arr: Ciphered, index: Ciphered, value: Ciphered, count: int,
+                    out_bound=None) -> Ciphered:
+        """A copy of the array batch arr with arr[i] = value per array, for an ENCRYPTED index
+        (hm_array_write_batch): arr.n == count * index.n, value.n == index.n, value.nbits ==
+        arr.nbits.  An index >= count writes nowhere.  The output keeps arr's plaintext dtype."""
+        self.validate_operation(HomomorphicArrayWrite, _ArrayOp.index_bits(count))
+        need = array_write_out_bounds(arr.bound, value.bound, count, index.bound)
+        out = Ciphered.empty(arr.n, need if out_bound is None else out_bound, self.device,
+                             arr.plain_dtype)
+        array_write_into(self, arr, index, value, count, out)
+        return out
+
     def mul_plan_work(self, a_bound, b_bound, k=None, signed=False) -> float:
         """hm_mul_plan_work: the carry products' word pairs as this context's plan runs them
         (Karatsuba products by their leaves) for the low k output bits (all when k is None)."""
@@ -1080,7 +1192,8 @@ class Context:
         """Context::apply_n (src/context.rs:535-546): validate `op`'s MIN_D_OVER_DELTA, then call
         the user operation `op.apply(ctx, args)` (HomomorphicOperation<N>, operations.rs:204-213:
         the crate ships no N-ary operation of its own; a user op composes the batched ones)."""
-        self.validate_operation(op)
+        if not _is_array(op):  # (an array op validates at its index bits, inside apply)
+            self.validate_operation(op)
         return op.apply(self, list(args))
 
     # ---- polynomial primitives
@@ -1200,6 +1313,26 @@ def bitcount_into(ctx: Context, op, a: Ciphered, out: Ciphered) -> None:
                                                 ctypes.byref(co)), "hm_bitcount_batch")
 
 
+def array_read_into(ctx: Context, arr: Ciphered, index: Ciphered, count: int,
+                    out: Ciphered) -> None:
+    """hm_array_read_batch into a preallocated output of index.n values (bounds:
+    array_read_out_bounds)."""
+    ca, ci, co = arr._c(), index._c(), out._c()
+    ctx._launch(lambda: lib().hm_array_read_batch(ctx._h, ctypes.byref(ca), int(count),
+                                                  ctypes.byref(ci), ctypes.byref(co)),
+                "hm_array_read_batch")
+
+
+def array_write_into(ctx: Context, arr: Ciphered, index: Ciphered, value: Ciphered, count: int,
+                     out: Ciphered) -> None:
+    """hm_array_write_batch into a preallocated output of arr.n values (bounds:
+    array_write_out_bounds)."""
+    ca, ci, cv, co = arr._c(), index._c(), value._c(), out._c()
+    ctx._launch(lambda: lib().hm_array_write_batch(ctx._h, ctypes.byref(ca), int(count),
+                                                   ctypes.byref(ci), ctypes.byref(cv),
+                                                   ctypes.byref(co)), "hm_array_write_batch")
+
+
 def minmax_into(ctx: Context, op, a: Ciphered, b: Ciphered, out: Ciphered, signed=None) -> None:
     """hm_minmax_batch (op: HomomorphicMin or HomomorphicMax) into a preallocated output
     (bounds: minmax_out_bounds).  signed defaults from a's plaintext dtype, as for comparisons."""
@@ -1240,3 +1373,17 @@ def pad_bits(c: Ciphered, nbits: int) -> Ciphered:
                      torch.zeros((c.n, extra), dtype=c.degree.dtype, device=c.degree.device)], dim=1)
     bound = np.concatenate([c.bound, np.zeros(extra, dtype=np.uint32)])
     return Ciphered(limbs, deg, bound, nbits, c.n, c.plain_dtype)
+
+
+def stack_values(parts) -> Ciphered:
+    """An array batch from N batches of equal n, nbits and bounds: value e * N + v of the result is
+    value e of parts[v] (a copy; what array_read and array_write take for count = N)."""
+    torch = _torch()
+    parts = list(parts)
+    c = parts[0]
+    for p in parts[1:]:
+        if p.n != c.n or p.nbits != c.nbits or not np.array_equal(p.bound, c.bound):
+            raise ValueError("stack_values takes batches of equal n, nbits and bounds")
+    limbs = torch.stack([p.limbs.view(p.n, p.stride) for p in parts], dim=1).reshape(-1)
+    deg = torch.stack([p.degree.view(p.n, p.nbits) for p in parts], dim=1).reshape(-1, c.nbits)
+    return Ciphered(limbs, deg, c.bound, c.nbits, c.n * len(parts), c.plain_dtype)

@@ -39,6 +39,7 @@ OP_LOOKUP = 17
 OP_SHL, OP_SHR, OP_ROTL, OP_ROTR = range(18, 22)
 (OP_COUNT_ONES, OP_COUNT_ZEROS, OP_LEADING_ZEROS, OP_LEADING_ONES, OP_TRAILING_ZEROS,
  OP_TRAILING_ONES) = range(22, 28)
+OP_ARRAY_READ, OP_ARRAY_WRITE = 28, 29
 
 u64p = ctypes.POINTER(ctypes.c_uint64)
 u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -127,6 +128,13 @@ SIGNATURES = {
     "hm_bitcount_out_bounds": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, u32p, u32p]),
     "hm_bitcount_batch": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(HmBatch),
                                          ctypes.POINTER(HmBatch)]),
+    "hm_array_read_out_bounds": (ctypes.c_int, [ctypes.c_uint32, u32p, ctypes.c_uint32, u32p, u32p]),
+    "hm_array_write_out_bounds": (ctypes.c_int, [ctypes.c_uint32, u32p, u32p, ctypes.c_uint32, u32p,
+                                                 u32p]),
+    "hm_array_read_batch": (ctypes.c_int, [vp, ctypes.POINTER(HmBatch), ctypes.c_uint32,
+                                           ctypes.POINTER(HmBatch), ctypes.POINTER(HmBatch)]),
+    "hm_array_write_batch": (ctypes.c_int, [vp, ctypes.POINTER(HmBatch), ctypes.c_uint32] +
+                             [ctypes.POINTER(HmBatch)] * 3),
     "hm_poly_add_batch": (ctypes.c_int, [vp] + [ctypes.POINTER(HmPolys)] * 3),
     "hm_poly_mul_batch": (ctypes.c_int, [vp] + [ctypes.POINTER(HmPolys)] * 3),
     "hm_poly_rem_batch": (ctypes.c_int, [vp, ctypes.POINTER(HmPolys), u64p, ctypes.c_size_t,

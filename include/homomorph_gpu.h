@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define HM_ABI_VERSION 10 /* 4: kernel timing by device stamps (HM_TIME_*), hm_ctx_last_hip_error;
+#define HM_ABI_VERSION 11 /* 4: kernel timing by device stamps (HM_TIME_*), hm_ctx_last_hip_error;
                             5: hm_ctx_clear_kernel_timing, hm_ctx_set_mul_scratch;
                             6: HM_OP_SUB .. HM_OP_GE, hm_sub_batch, hm_compare_batch, their bounds,
                                hm_validate_operation_bits;
@@ -43,7 +43,9 @@ extern "C" {
                             8: HM_OP_LOOKUP, hm_lookup_batch, hm_lookup_out_bounds;
                             9: HM_OP_SHL .. HM_OP_ROTR, hm_shift_batch, hm_shift_out_bounds;
                             10: HM_OP_COUNT_ONES .. HM_OP_TRAILING_ONES, hm_bitcount_batch,
-                               hm_bitcount_out_bounds */
+                               hm_bitcount_out_bounds;
+                            11: HM_OP_ARRAY_READ, HM_OP_ARRAY_WRITE, hm_array_read_batch,
+                               hm_array_write_batch, their bounds */
 #define HM_MAX_BITS 128 /* u128 is the widest type with impls (src/impls/numbers/uint.rs:58) */
 
 typedef enum hm_status {
@@ -132,6 +134,14 @@ typedef enum hm_op {
     HM_OP_LEADING_ONES = 25,   /* HomomorphicLeadingOnes      a.leading_ones() */
     HM_OP_TRAILING_ZEROS = 26, /* HomomorphicTrailingZeros    a.trailing_zeros() */
     HM_OP_TRAILING_ONES = 27,  /* HomomorphicTrailingOnes     a.trailing_ones() */
+    /* Oblivious array read and write by an ENCRYPTED index (hm_array_read_batch,
+     * hm_array_write_batch) over an array of count elements, count in 2..256, k = ceil(log2 count)
+     * index bits.  Both multiply an indicator of k literals by one element or value bit, so
+     * m = k + 1 and min d/delta 2k + 3 (count 2: 5, 4: 7, 16: 11, 256: 19).  Width dependent
+     * (hm_validate_operation_bits), and the width is k, the number of index bits, in 1..8, as for
+     * HM_OP_LOOKUP; for fresh operands. */
+    HM_OP_ARRAY_READ = 28,     /* HomomorphicArrayRead        arr[i] */
+    HM_OP_ARRAY_WRITE = 29,    /* HomomorphicArrayWrite       arr[i] = x */
 } hm_op;
 
 typedef struct hm_ctx hm_ctx;
@@ -384,6 +394,20 @@ hm_status hm_shift_out_bounds(hm_op which, uint32_t nbits, const uint32_t *a_bou
  * HM_ERR_UNSUPPORTED. */
 hm_status hm_bitcount_out_bounds(hm_op which, uint32_t nbits, const uint32_t *a_bound,
                                  uint32_t out_bound[8]);
+/* Output bounds of hm_array_read_batch(arr, count, index) on nbits-bit elements (nbits in 1..128),
+ * count in 2..256 (anything else is HM_ERR_INVALID_ARGUMENT, as is a null pointer).  arr_bound:
+ * nbits entries, shared by all elements; s_bound: the k = ceil(log2 count) bounds of the index's
+ * low bits.  With S the sum of s_bound, out_bound[j] = S + arr_bound[j].  (u8 x 16 at d + dp = 256,
+ * a u8 index: every bit 1280, 168 limbs per value.)  A bound beyond the engine's degree range is
+ * HM_ERR_UNSUPPORTED. */
+hm_status hm_array_read_out_bounds(uint32_t nbits, const uint32_t *arr_bound, uint32_t count,
+                                   const uint32_t *s_bound, uint32_t *out_bound);
+/* Output bounds of hm_array_write_batch(arr, count, index, value): as above with x_bound the nbits
+ * bounds of the value written; out_bound[j] = S + max(arr_bound[j], x_bound[j]), shared by all
+ * elements of the output array. */
+hm_status hm_array_write_out_bounds(uint32_t nbits, const uint32_t *arr_bound,
+                                    const uint32_t *x_bound, uint32_t count,
+                                    const uint32_t *s_bound, uint32_t *out_bound);
 /* stride (limbs per value) of a batch with these bounds */
 uint64_t hm_batch_stride(uint32_t nbits, const uint32_t *bound);
 
@@ -538,6 +562,52 @@ hm_status hm_shift_batch(hm_ctx *ctx, hm_op which, const hm_batch *a, const hm_b
  * u32 at D = 512 and u64 at D = 256 do not fit (a u64 count at 256 would keep E_1 .. E_32, 4288
  * words), and u128 runs up to D = 32 (a count up to D = 16). */
 hm_status hm_bitcount_batch(hm_ctx *ctx, hm_op which, const hm_batch *a, hm_batch *out);
+
+/* arr[i] per value for an ENCRYPTED index i: oblivious memory's read.  An array of count elements,
+ * count any integer in 2..256, is count consecutive values of an ordinary batch: element v of
+ * array e is value e * count + v, and all elements share the batch's bound[] (what hm_encrypt_batch
+ * of n * count plaintext values gives).  k = ceil(log2 count); index is read in place and only its
+ * low k ciphertext bits s_0 .. s_{k-1} are read and validated (index->nbits >= k), so a
+ * Ciphered<u8> or a Ciphered<u32> can index.  With v_t bit t of v, the indicator of element v is
+ *   ind_v = prod_t (s_t + 1 + v_t)           (the literal s_t where v_t = 1, s_t + 1 where 0)
+ *   out_j = sum over v < count of ind_v T_{v,j}             (T_{v,j}: bit j of element v)
+ * so an index >= count reads 0.  It is evaluated as a multiplexer tree, y = L + s_t (L + R) at
+ * level t, a right sibling past the array being the null polynomial: one product per tree node
+ * with an element below it (count - 1 per output bit for a power of two).  Every output bit is one
+ * fixed polynomial of the inputs whatever the order of evaluation: exact in GF(2)[X] (for null /
+ * unit elements, the polynomials hm_lookup_batch gives for the same table).  A null s_t takes the
+ * left child, the unit polynomial the right.  n = index->n = out->n values; arr->n == count * n:
+ * one array per value; arr->n == count: ONE SHARED TABLE read by every index (a private query);
+ * anything else is HM_ERR_INVALID_ARGUMENT.  out: out->nbits == arr->nbits, bounds from
+ * hm_array_read_out_bounds over the index's first k bounds (larger ones are accepted, smaller ones
+ * HM_ERR_INVALID_ARGUMENT); out may not overlap arr or index, in limbs or in degree words
+ * (HM_ERR_INVALID_ARGUMENT).  count outside 2..256, index->nbits < k or a null pointer is
+ * HM_ERR_INVALID_ARGUMENT; n == 0 is HM_OK.  Every bit of every element and the k index bits are
+ * read and validated.  Validates HM_OP_ARRAY_READ at k: the requirement covers fresh operands;
+ * operands that came out of another operation carry that operation's depth, which the caller
+ * accounts for.  One launch, no workspace: per output bit a wave keeps one waiting left child per
+ * tree level in LDS; HM_ERR_UNSUPPORTED (before any launch) when that does not fit a wavefront's
+ * share of LDS, the bit counts' 2560 words.  The slice does not depend on the element width: at
+ * one bound D on every bit, count 256 takes 624 words at D = 256, 1192 at D = 512 and 2328 at
+ * D = 1024; D = 2048 is refused. */
+hm_status hm_array_read_batch(hm_ctx *ctx, const hm_batch *arr, uint32_t count,
+                              const hm_batch *index, hm_batch *out);
+/* arr[i] = x per value for an ENCRYPTED index i, out of place: oblivious memory's write.  Array
+ * layout, count, k and the index as for hm_array_read_batch;
+ *   out_{v,j} = T_{v,j} + ind_v (x_j + T_{v,j})       for every v < count
+ * so an index >= count writes nowhere.  Each indicator is formed once per array, as the suffix
+ * products prod_{i >= t} lit_i(v): stepping v forms again only the levels at or below its lowest
+ * set bit, about two products per element.  Exact in GF(2)[X]; a null indicator makes its element
+ * an exact copy.  value->nbits == arr->nbits == out->nbits, value->n == index->n == n,
+ * arr->n == out->n == count * n (no shared form); bounds from hm_array_write_out_bounds (larger
+ * ones are accepted, smaller ones HM_ERR_INVALID_ARGUMENT); out may not overlap arr, index or
+ * value (HM_ERR_INVALID_ARGUMENT).  Argument errors, n == 0, validation (HM_OP_ARRAY_WRITE at k)
+ * and what is read as for the read, with every bit of value.  One launch, no workspace: the index
+ * bits, the k suffix products and all of value's bits stay in LDS for the array; count 256 at
+ * D = 256 takes 592 words for u8 elements, 856 for u32 and 1912 for u128 ones
+ * (HM_ERR_UNSUPPORTED beyond 2560: u128 elements at D = 512, u32 x 256 at D = 1024). */
+hm_status hm_array_write_batch(hm_ctx *ctx, const hm_batch *arr, uint32_t count,
+                               const hm_batch *index, const hm_batch *value, hm_batch *out);
 
 /* ---------------- polynomial primitives (src/polynomial.rs), for unit parity ---------------- */
 /* Polynomial::add (polynomial.rs:190-213) per pair: out = a ^ b, exact degree. */

@@ -1,7 +1,7 @@
-"""Register and segment figures of the eight wave-per-value circuit kernels (kernels.hip), from the
+"""Register and segment figures of the ten wave-per-value circuit kernels (kernels.hip), from the
 compiler's own metadata: kernels.hip is compiled for gfx950 to assembly (device only, no GPU
 needed) and the VGPRs, SGPRs, private segment, spill counts and kernarg size of gate, borrow,
-minmax, select, lookup, shift, bitcount and bitrun are read from it; tools/kernarg_audit.py's findings are counted
+minmax, select, lookup, shift, bitcount, bitrun, array_read and array_write are read from it; tools/kernarg_audit.py's findings are counted
 beside them.
 
 usage: circuit_resources.py [--src homomorph-rust_amd/csrc/kernels.hip] [--label new]
@@ -20,7 +20,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import kernarg_audit  # noqa: E402
 
-KERNELS = ("gate", "borrow", "minmax", "select", "lookup", "shift", "bitcount", "bitrun")
+KERNELS = ("gate", "borrow", "minmax", "select", "lookup", "shift", "bitcount", "bitrun",
+           "array_read", "array_write")
 FIELDS = {"vgpr_count": "vgprs", "sgpr_count": "sgprs", "private_segment_fixed_size": "private",
           "vgpr_spill_count": "vgpr_spills", "sgpr_spill_count": "sgpr_spills",
           "kernarg_segment_size": "kernarg_bytes"}
