@@ -168,6 +168,47 @@ inline hm_status plan_chain(const AddShape &S, AddArgs &A) {
     return HM_OK;
 }
 
+// MFMAs the NC-chunk chain issues for one bit whose carry has nc words, P_i np and ab_i nab
+// (adder_mfma.hip's tile loop): NC per tile, and with trimming the top tile's bucket of live chunks
+// (engine.h chain_trim_bucket).  A null carry or P_i runs no tile.
+constexpr uint32_t chain_bit_mfmas(int NC, int nc, int np, int nab, bool trim) {
+    if (nc <= 0 || np <= 0) return 0;
+    const int tiles = ((nc + np > nab ? nc + np : nab) + 31) >> 5;
+    const int top = trim ? chain_trim_bucket(NC, chain_top_live(NC, nc, np, tiles)) : NC;
+    return (uint32_t)(NC * (tiles - 1) + top);
+}
+
+// ... and for one value over the whole add when every degree is at its static bound (slot_walk's
+// carry-bound recurrence); a(i), b(i): the operands' bounds.  top_live, when given, counts the
+// bits by their top tile's live chunks (NC + 1 entries).
+template <class FA, class FB>
+constexpr uint64_t chain_mfma_walk(uint32_t nbits, FA a, FB b, int NC, bool trim, uint32_t *top_live = nullptr) {
+    uint64_t count = 0;
+    int64_t cb = -1;
+    for (uint32_t i = 0; i + 1 < nbits; ++i) {
+        const int64_t ba = a(i), bb = b(i);
+        const int64_t x = ba > bb ? ba : bb, ab = ba + bb, p = x + ab;
+        const int nc = (int)words_of_bound(cb), np = (int)words_of_bound(p), nab = (int)words_of_bound(ab);
+        count += chain_bit_mfmas(NC, nc, np, nab, trim);
+        if (top_live && nc > 0) ++top_live[chain_top_live(NC, nc, np, ((nc + np > nab ? nc + np : nab) + 31) >> 5)];
+        cb = (cb < 0) ? ab : (ab > p + cb ? ab : p + cb);
+    }
+    return count;
+}
+inline uint64_t chain_mfma_count(const AddShape &S, int NC, bool trim, uint32_t *top_live = nullptr) {
+    return chain_mfma_walk(S.nbits, [&](uint32_t i) { return S.a[i]; }, [&](uint32_t i) { return S.b[i]; }, NC,
+                           trim, top_live);
+}
+// The headline (u32, every bound d + d' = 256): DESIGN.md 4.1's 4,979 MFMAs per value untrimmed,
+// 4,860 with the buckets 13, 12, 8, 4 (4,791 if every dead chunk were skipped); configs[0]'s u8
+// add at 128 and configs[4]'s u32 add at 512 beside it.
+constexpr uint64_t chain_mfma_uniform(uint32_t nbits, uint32_t B, int NC, bool trim) {
+    return chain_mfma_walk(nbits, [B](uint32_t) { return B; }, [B](uint32_t) { return B; }, NC, trim);
+}
+static_assert(chain_mfma_uniform(32, 256, 13, false) == 4979 && chain_mfma_uniform(32, 256, 13, true) == 4860);
+static_assert(chain_mfma_uniform(8, 128, 7, false) == 91 && chain_mfma_uniform(8, 128, 7, true) == 83);
+static_assert(chain_mfma_uniform(32, 512, 25, false) == 18750 && chain_mfma_uniform(32, 512, 25, true) == 18360);
+
 } // namespace add_plan
 
 inline hm_status plan_add(const AddShape &S, AddArgs &A) {

@@ -37,6 +37,8 @@
 // bit 0 of its f32 encoding is the coefficient.  One v_alignbit per accumulator gathers them.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "mfma_gf2.h"
 
 namespace hm {
@@ -84,7 +86,16 @@ template <int NC> constexpr int kPrefetchOf = NC > 16 ? HM_MFMA_PREFETCH25 : NC 
 // three stages, its LDS latency hidden under this tile's MFMAs instead of stalling the wave between
 // tiles
 template <int NC> constexpr int kStage(int k) { return NC <= 8 ? 2 * k : 1 + 3 * k; }
-template <int NC, class Side, int kPrefetch = kPrefetchOf<NC>>
+// LC <= NC: the live chunks.  A bit's top tile whose window reaches the carry with its first L
+// chunks only (engine.h chain_top_live) runs the body with the smallest LC >= L the kernel has:
+// chunks LC .. NC - 1 and their B reads are not issued (they multiply zero carry words; nothing
+// depends on skipping them).  LC = NC is every other tile's body.
+// kNext = false (the trimmed kernel's top tile, whatever its LC): the body does not fetch the next
+// tile's first fragments; the caller reads them before the loop over the other tiles, as the
+// untrimmed kernel reads the top tile's before its loop.  (Fetched inside the top tile's bodies
+// they reached the loop in twelve registers of their own, and the loop, short of registers for
+// its B fragments, was compiled with lgkmcnt(0) before five of its MFMAs.)
+template <int NC, int LC, bool kNext, class Side, int kPrefetch = kPrefetchOf<NC>>
 __device__ __forceinline__ v16f tile_mfma(const v8i (&Af)[NC], uint32_t rb, uint32_t rbn,
                                           u32x4 (&pf)[kPrefetch], v16f acc, Side &&side) {
     // rb, rbn: LDS byte addresses of this tile's and the next tile's window (one VGPR each; the
@@ -93,13 +104,15 @@ __device__ __forceinline__ v16f tile_mfma(const v8i (&Af)[NC], uint32_t rb, uint
     // ring fill is side stage 2, issued above them), so the next tile's first MFMA does not wait
     // for the LDS
     static_assert(NC - kPrefetch > kStage<NC>(2), "next tile's B reads must follow its ring fill (stage 2)");
-    u32x4 bq[NC];
+    static_assert(LC >= 1 && LC <= NC, "live chunks");
+    static_assert(!kNext || LC == NC, "only the full body fetches the next tile's fragments");
+    u32x4 bq[LC];
 #pragma unroll
-    for (int c = 0; c < kPrefetch; ++c) bq[c] = pf[c];
+    for (int c = 0; c < kPrefetch && c < LC; ++c) bq[c] = pf[c];
 #pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        if (c + kPrefetch < NC) bq[c + kPrefetch] = lds_at<const u32x4>(rb)[2 * (c + kPrefetch)];
-        else pf[c + kPrefetch - NC] = lds_at<const u32x4>(rbn)[2 * (c + kPrefetch - NC)];
+    for (int c = 0; c < LC; ++c) {
+        if (c + kPrefetch < LC) bq[c + kPrefetch] = lds_at<const u32x4>(rb)[2 * (c + kPrefetch)];
+        else if (kNext) pf[c + kPrefetch - LC] = lds_at<const u32x4>(rbn)[2 * (c + kPrefetch - LC)];
         const v8i Bf = {(int)bq[c].x, (int)bq[c].y, (int)bq[c].z, (int)bq[c].w, 0, 0, 0, 0};
         acc = mfma_fp4(Af[c], Bf, acc);
         asm volatile("" : "+v"(acc)::"memory");
@@ -107,7 +120,26 @@ __device__ __forceinline__ v16f tile_mfma(const v8i (&Af)[NC], uint32_t rb, uint
         if (c == kStage<NC>(1)) side(1);
         if (c == kStage<NC>(2)) side(2);
     }
+    // the side stages whose chunk slot is cut off run after the last MFMA, in order: the top tile
+    // is the first one run, and the tile below it needs its window filled all the same
+    // (stage 0 sits after chunk 1, or 0 at NC = 7, and the smallest buckets are 4, 2 and 8: no
+    // instance cuts it off)
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        if (kStage<NC>(k) >= LC) side(k);
     return acc;
+}
+
+// The whole tile step f(live chunks as a type) of the bucket lc (engine.h chain_trim_lc), by scalar
+// compares from the full body down (lc is wave-uniform; the last bucket needs no compare).  Each
+// bucket has its own copy of the step, parity gather and stores included: bodies that met again
+// before the gather, or inside the loop over the tiles, spilled 10 to 69 VGPRs.
+template <int NC, int J, class F> __device__ __forceinline__ void top_tile(int lc, F &&f) {
+    constexpr int LC = chain_trim_lc(NC, J);
+    if constexpr (J + 1 < kChainTrimBuckets) {
+        if (lc != LC) return top_tile<NC, J + 1>(lc, f);
+    }
+    f(std::integral_constant<int, LC>{});
 }
 
 // Ring slot of carry word w during bit i: (w + D) % kMfmaRingSlots with D = np, the words of P_i
@@ -150,6 +182,31 @@ __device__ __forceinline__ void sum_store(uint64_t base, uint32_t off, uint32_t 
     asm volatile("global_store_dword %0, %1, %2" : : "v"(off), "v"(v), "s"(base) : "memory");
 }
 
+// store_sum_x (dev_common.h) with its stores in that form: s = x ^ carry to dst (a wave-uniform
+// address), the degree word and the capacity check.  The trimmed kernel's first bits take it: the
+// per-lane 64-bit address of the plain form stayed in a VGPR pair across the bit loop.
+__device__ __forceinline__ int store_sum_x_sbase(const uint32_t *X, int nx, const uint32_t *C, int nc, uint64_t *dst,
+                                                 uint32_t bound, uint32_t *deg_out, int *status) {
+    const int lane = lane_opaque();
+    const int cap = (int)cap_of(bound);
+    const int total = max(cap, (max(nx, nc) + 1) / 2);
+    const uint64_t base = (uint64_t)(uintptr_t)dst;
+    int ldeg = -1;
+    for (int g = lane; g < total; g += kWave) {
+        const int w = 2 * g;
+        const uint32_t lo = (w < nx ? X[w] : 0u) ^ (w < nc ? C[w] : 0u);
+        const uint32_t hi = (w + 1 < nx ? X[w + 1] : 0u) ^ (w + 1 < nc ? C[w + 1] : 0u);
+        if (g < cap) sum_store(base, 8u * (uint32_t)g, lo), sum_store(base, 8u * (uint32_t)g + 4u, hi);
+        if (lo | hi) ldeg = hi ? w * 32 + 63 - (int)__builtin_clz(hi) : w * 32 + 31 - (int)__builtin_clz(lo);
+    }
+    const int deg = wave_max_i32(ldeg);
+    if (lane == 0) {
+        if (deg > (int)bound) flag(status, HM_ERR_CAPACITY);
+        *deg_out = (uint32_t)max(deg, 0);
+    }
+    return deg;
+}
+
 // s_getreg_b32 operands: register id | first bit << 6 | (bits - 1) << 11
 constexpr int kGetregHwId = 4 | 31 << 11;         // HW_REG_HW_ID: wave slot [3:0], SIMD [5:4], CU [11:8], SH [12], SE [15:13]
 constexpr int kGetregWaveSlot = 4 | 3 << 11;      // its WAVE_ID field
@@ -171,6 +228,18 @@ constexpr int kGetregXccId = 20 | 3 << 11;        // HW_REG_XCC_ID [3:0]
 #endif
 static_assert(HM_CHAIN_PRIO == 0 || HM_CHAIN_PRIO == 2, "HM_CHAIN_PRIO: 0 (by age) or 2 (rotating levels)");
 template <int NC> constexpr int kChainPrio = NC == 13 ? HM_CHAIN_PRIO : 0;
+// Top-tile trimming (DESIGN.md 4.1 "Top-tile trimming"): each bit's top tile, the first one run,
+// takes the tile body of its live-chunk bucket, chosen on the scalar unit before the tile's MFMAs;
+// every other tile runs the full body.  A mask of instances: 1 NC = 7, 2 NC = 13, 4 NC = 25
+// (0: the untrimmed kernel, the parent of the A/B).  Kept where it won every one of four
+// alternating rounds (profiles/chain_trim/): NC = 13 (headline step 0.4729-0.4820 -> 0.4664-0.4674
+// ms) and NC = 25 (configs[4]'s add chunk 50.36-50.51 -> 50.06-50.23 ms); NC = 7 lost
+// (configs[0]'s u8 add 383-390 -> 390-397 us: one to three tiles a bit, and four bodies of code
+// for them) and stays untrimmed.
+#ifndef HM_CHAIN_TRIM
+#define HM_CHAIN_TRIM 6
+#endif
+template <int NC> constexpr bool kChainTrim = ((HM_CHAIN_TRIM) >> (NC <= 8 ? 0 : NC <= 16 ? 1 : 2)) & 1;
 // s_setprio takes an immediate: a wave-uniform level (an SGPR) selects one by scalar branches
 __device__ __forceinline__ void set_prio(uint32_t level) {
     if (level == 0) __builtin_amdgcn_s_setprio(0);
@@ -226,6 +295,14 @@ add_chain_mfma_kernel(AddArgs A) {
     const uint32_t *ws = A.ws + e * A.ws_stride;
     uint64_t *po = A.out.limbs + e * A.out.stride;
     uint32_t *dout = A.out.degree + e * L;
+    if constexpr (kChainTrim<NC>) {
+        // wave-uniform by hand (as wsu and son below): the two bases lived in four VGPRs for the
+        // whole kernel, which the top tile's bodies need
+        // (the offsets, not the pointers: a pointer rebuilt from an integer is a flat one, and a
+        // flat store in flight makes every LDS wait of the bit an lgkmcnt(0))
+        auto uniform = [](uint64_t v) { return ((uint64_t)rfl((uint32_t)(v >> 32)) << 32) | rfl((uint32_t)v); };
+        po = A.out.limbs + uniform(e * A.out.stride), dout = A.out.degree + uniform(e * L);
+    }
     // Bit i's workspace record, copied into stage[wave][i&1] by one LDS-DMA a bit ahead (its
     // latency hides behind the previous bit's tiles): [x_i: cntX][P_i: cntP][ab_i: cntAB][deg P_i]
     // [deg ab_i] (host plan: at most kRec words, one DMA per 64).  The DMA is asm: the compiler cannot tell the
@@ -289,7 +366,9 @@ add_chain_mfma_kernel(AddArgs A) {
         HM_PT(t0);
         HM_PACC(3, tw0, t0);
         if (tw < 0) {
-            store_sum_x(rec, (int)A.cntX, C, nc, po + offo, A.ob.b[i], dout + i, A.status);
+            if constexpr (kChainTrim<NC>)
+                store_sum_x_sbase(rec, (int)A.cntX, C, nc, po + offo, A.ob.b[i], dout + i, A.status);
+            else store_sum_x(rec, (int)A.cntX, C, nc, po + offo, A.ob.b[i], dout + i, A.status);
         } else {
             // the tiles T >= 1 wrote s_i's words from 32 up (= carry words there); left: words
             // 0..31 (x_i ^ carry; stored here rather than by tile 0, whose stores would still be
@@ -299,11 +378,19 @@ add_chain_mfma_kernel(AddArgs A) {
             int ldeg = -1;
             if (lane < 32) { // C is valid up to tw >= 32 words; cntX < 32
                 const uint32_t v = (lane < (int)A.cntX ? rec[lane] : 0u) ^ C[lane];
-                if (lane < capw) so[lane] = v;
+                if (lane < capw) {
+                    // (trimmed kernel: from the scalar base, as the tiles' stores; the compiler
+                    // kept po + 4 lane in a VGPR pair across the bit loop)
+                    if constexpr (kChainTrim<NC>) sum_store((uint64_t)(uintptr_t)so, 4u * (uint32_t)lane, v);
+                    else so[lane] = v;
+                }
                 // (a word past the capacity still counts: the degree check below flags it)
                 if (v) ldeg = lane * 32 + 31 - (int)__builtin_clz(v);
             }
-            for (int w = tw + lane; w < capw; w += kWave) so[w] = 0u;
+            for (int w = tw + lane; w < capw; w += kWave) {
+                if constexpr (kChainTrim<NC>) sum_store((uint64_t)(uintptr_t)so, 4u * (uint32_t)w, 0u);
+                else so[w] = 0u;
+            }
             int deg = wave_max_i32(ldeg);
             if (nc > 32) deg = degc; // the carry's top word is above the words stored here
             if (lane == 0) {
@@ -432,7 +519,19 @@ add_chain_mfma_kernel(AddArgs A) {
         // ab_i's word of the tile's output: zero above ab_i's tiles (tiles 0 and 1 at most: ab_i <
         // 64 words, host plan), so it is set once here and read only behind a wave-uniform branch
         uint32_t abw = 0u;
-        for (int T = tiles - 1; T >= 0; --T) {
+        // the top tile's bucket of live chunks (wave-uniform: nc, np and tiles are)
+        [[maybe_unused]] int lc = NC;
+        if constexpr (kChainTrim<NC>) {
+            const int live = chain_top_live(NC, nc, np, tiles);
+#pragma unroll
+            for (int j = 1; j < kChainTrimBuckets; ++j)
+                if (live <= chain_trim_lc(NC, j)) lc = chain_trim_lc(NC, j);
+            lc = (int)rfl((uint32_t)lc);
+        }
+        // One tile; lct: its live chunks as a type (the full body NC, or the top tile's bucket)
+        auto tile_step = [&](const int T, auto lct, auto next) {
+            constexpr int LC = decltype(lct)::value;
+            constexpr bool kNext = decltype(next)::value;
             wsync(); // ring images of this tile's window are written
             if constexpr (NC > 16) rb = rbase(T); // (NC = 25: carried over, it spilled)
             // the next tile's 32 new window words (old carry: below 32T; their ring slots, phase
@@ -453,7 +552,7 @@ add_chain_mfma_kernel(AddArgs A) {
                 abw = W < nab ? abi[W] : 0u;
             }
             if constexpr (kPrio == 0) __builtin_amdgcn_s_setprio(1); // the MFMA phase keeps the pipe
-            acc = tile_mfma<NC>(Af, rb, rbn, pf, acc, [&](int stage) {
+            auto side = [&](int stage) {
                 // (the empty asm keep each stage's arithmetic from being hoisted into an earlier
                 // stage, where it would wait for the read of the stage before)
                 if (stage == 0) {
@@ -468,7 +567,8 @@ add_chain_mfma_kernel(AddArgs A) {
                     *lds_at<u32x2>(pp) = fn;
                     if (mirror) *lds_at<u32x2>(pp + 16u * kMfmaRingSlots) = fn;
                 }
-            });
+            };
+            acc = tile_mfma<NC, LC, kNext>(Af, rb, rbn, pf, acc, side);
             if constexpr (kPrio == 0) __builtin_amdgcn_s_setprio(0);
             // accumulator j of lane half h is output bit j + 16h (row-permuted tiles): its parity
             // is bit 16 + j of tnow; XOR the bits of the accumulators before this tile
@@ -510,7 +610,17 @@ add_chain_mfma_kernel(AddArgs A) {
             rb = rbn;
             cF -= 128u;
             cW -= 128u;
+        };
+        int T = tiles - 1;
+        if constexpr (kChainTrim<NC>) {
+            top_tile<NC, 0>(lc, [&](auto lct) { tile_step(T, lct, std::false_type{}); });
+            --T;
+            // the next tile's first fragments (its ring fill, the top tile's side stage 2, is
+            // issued; a one-tile bit reads a phase that nothing uses, as tile 0 always has)
+#pragma unroll
+            for (int c = 0; c < kPrefetch; ++c) pf[c] = lds_at<const u32x4>(rbase(T))[2 * c];
         }
+        for (; T >= 0; --T) tile_step(T, std::integral_constant<int, NC>{}, std::true_type{});
         const int deg = track ? wave_max_i32(ldeg) : alg;
         nc = deg >= 0 ? (deg >> 5) + 1 : 0;
         degc = deg;
@@ -528,7 +638,16 @@ add_chain_mfma_kernel(AddArgs A) {
         g[7] = (unsigned long long)__builtin_amdgcn_s_getreg(kGetregXccId) << 32 | __builtin_amdgcn_s_getreg(kGetregHwId);
     }
 #endif
-    kt_finish(A.kt);
+    if constexpr (kChainTrim<NC>) {
+        // kt_finish from the scalar wave index, the launch's waves per block and a lane id made
+        // here: threadIdx.x and blockDim.x are not kept in VGPRs (they were spilled) from the
+        // kernel's entry to its end
+        if (A.kt.t1 && lane_opaque() == 0)
+            __hip_atomic_fetch_max(&A.kt.t1[(blockIdx.x * (uint32_t)kMfmaWpb + (uint32_t)wave) & (kTimerWaves - 1)],
+                                   (unsigned long long)wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+        kt_finish(A.kt);
+    }
 }
 
 int launch_add_chain_mfma(const AddArgs &a, void *stream) {

@@ -678,6 +678,25 @@ template <int NC> struct MfmaCfg {
     static_assert(2 * NC - 1 <= kMirror, "ring mirror");
     static_assert(32 + 2 * NC + 32 <= kMfmaRingSlots, "ring window");
 };
+// Top-tile trimming (adder_mfma.hip "HM_CHAIN_TRIM"): chunk c of a bit's top tile T reads carry
+// words from 32 T - np + 2 c up, so only its first L = ceil((nc + np - 32 T) / 2) chunks reach the
+// carry's nc words.  The kernel has one tile body per bucket of L and runs the smallest bucket
+// >= L; add_host.h counts the MFMAs with the same functions.  Buckets, from the full body down:
+// NC, 3 s, 2 s, s with s = (NC - 1) / 3 (NC = 13: 13, 12, 8, 4; NC = 7: 7, 6, 4, 2; NC = 25: 25,
+// 24, 16, 8).  Fresh operands of d + d' = 32 (NC - 1) / 3 bits have P_i of NC - 1 chunks' words,
+// nc + np grows by 3/4 of a tile a bit, and L takes four values s apart, bit after bit: at the
+// headline's measured degrees 3-4, 7-8, 11-12 and 13 (DESIGN.md 4.1 has the histogram).
+constexpr int chain_top_live(int NC, int nc, int np, int tiles) {
+    const int L = (nc + np - 32 * (tiles - 1) + 1) >> 1;
+    return L < 0 ? 0 : L > NC ? NC : L;
+}
+constexpr int kChainTrimBuckets = 4;
+constexpr int chain_trim_lc(int NC, int j) { return j == 0 ? NC : (kChainTrimBuckets - j) * ((NC - 1) / 3); }
+constexpr int chain_trim_bucket(int NC, int L) {
+    int j = kChainTrimBuckets - 1;
+    while (chain_trim_lc(NC, j) < L) --j;
+    return chain_trim_lc(NC, j);
+}
 constexpr size_t kEncTableBytes = 96 * 1024; // largest encryption nibble table staged in LDS
                                               // (tau = 256 at d + dp = 512: 80 KB)
 

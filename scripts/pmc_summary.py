@@ -15,4 +15,4 @@ for f in sorted(glob.glob(os.path.join(root, "**", "*counter_collection.csv"), r
 for k, d in agg.items():
     print("--", k)
     for c, v in sorted(d.items()):
-        print(f"   {c:28s} n={len(v):3d} mean={sum(v)/len(v):.4g}")
+        print(f"   {c:28s} n={len(v):3d} mean={sum(v)/len(v):.6g}")

@@ -8,6 +8,7 @@
 #define HM_MFMA_PROFILE 1
 #endif
 #include "../homomorph-rust_amd/csrc/adder_mfma.hip"
+#include "../homomorph-rust_amd/csrc/add_host.h"
 
 #include <algorithm>
 #include <cmath>
@@ -38,7 +39,30 @@ static int run_case(int L, int npw, int abw, int mode, int pbit, int cbit, bool 
 
 static int timing(int nvals, bool wide);
 
+// The static count (add_host.h chain_mfma_count): MFMAs per value at uniform input bounds B over
+// nbits bits on the NC-chunk chain, untrimmed and with top-tile trimming, and the bits by their top
+// tile's live chunks.  No GPU call.
+static void static_count(const char *what, int NC, uint32_t nbits, uint32_t B) {
+    std::vector<uint32_t> b(nbits, B);
+    const AddShape S{nbits, b.data(), b.data(), 1, HM_ADD_CHAIN_MFMA, true};
+    std::vector<uint32_t> hist(NC + 1, 0u);
+    const uint64_t full = add_plan::chain_mfma_count(S, NC, false, hist.data());
+    const uint64_t trim = add_plan::chain_mfma_count(S, NC, true);
+    printf("%s (NC = %d, %u bits, bound %u): %llu MFMAs per value, %llu trimmed (kernel built with HM_CHAIN_TRIM %d: %s)\n  bits by live chunks L of the top tile:",
+           what, NC, nbits, B, (unsigned long long)full, (unsigned long long)trim, HM_CHAIN_TRIM,
+           (NC == 7 ? kChainTrim<7> : NC == 13 ? kChainTrim<13> : kChainTrim<25>) ? "trims" : "does not trim");
+    for (int l = 0; l <= NC; ++l)
+        if (hist[l]) printf(" %d: %u", l, hist[l]);
+    printf("\n");
+}
+
 int main(int argc, char **argv) {
+    if (argc > 1 && !strcmp(argv[1], "count")) {
+        static_count("headline u32 add, d + d' = 256", 13, 32, 256);
+        static_count("configs[0] u8 add, d + d' = 128", 7, 8, 128);
+        static_count("configs[4] u32 add, d + d' = 512", 25, 32, 512);
+        return 0;
+    }
     if (argc > 1 && !strcmp(argv[1], "time")) return timing(argc > 2 ? atoi(argv[2]) : 4096, false);
     if (argc > 1 && !strcmp(argv[1], "time25")) return timing(argc > 2 ? atoi(argv[2]) : 131072, true);
     if (argc > 1 && (!strcmp(argv[1], "sweep") || !strcmp(argv[1], "sweep25"))) {
@@ -336,6 +360,26 @@ static int timing(int nvals, bool wide) {
     int st = 0;
     hipMemcpy(&st, dst, 4, hipMemcpyDeviceToHost);
     if (st) printf("status %d: the record is outside the plan the timing stands for\n", st);
+    {
+        // MFMAs this launch issues, from the records' own degrees (deg carry_{i+1} = deg P_i + deg
+        // carry_i here: it is above deg ab_i from bit 1 on), summed over the values
+        const int NC = wide ? 25 : 13;
+        uint64_t full = 0, trim = 0;
+        for (int v = 0; v < nvals; ++v) {
+            const uint32_t *w = &ws[(size_t)v * A.ws_stride];
+            int degc = -1;
+            for (int i = 0; i + 1 < L; ++i) {
+                const int dab = (int)w[L * (cntAB + cntP) + i] - 1, dp = (int)w[L * (cntAB + cntP) + L + i] - 1;
+                const int nc = degc < 0 ? 0 : degc / 32 + 1, np = dp < 0 ? 0 : dp / 32 + 1, nab = dab < 0 ? 0 : dab / 32 + 1;
+                full += add_plan::chain_bit_mfmas(NC, nc, np, nab, false);
+                trim += add_plan::chain_bit_mfmas(NC, nc, np, nab, true);
+                degc = nc && np ? std::max(dp + degc, dab) : dab;
+            }
+        }
+        printf("MFMAs per launch from the records' degrees: %llu untrimmed, %llu trimmed (this build %s)\n",
+               (unsigned long long)full, (unsigned long long)trim,
+               (wide ? kChainTrim<25> : kChainTrim<13>) ? "trims" : "does not trim");
+    }
 #ifdef HM_MFMA_PROFILE
     std::vector<unsigned long long> hp((size_t)nvals * kMfmaProfSlots);
     hipMemcpy(hp.data(), dprof, hp.size() * 8, hipMemcpyDeviceToHost);
