@@ -12,6 +12,12 @@ at word and limb edges and the null / unit polynomials at every bit position.
 
 A polynomial is a Python int (bit k = coefficient of X^k), a value the list of its bit
 polynomials, least significant first (the model form of oracle/gf2_model.py).
+
+The second half of the module holds the families of the wave-per-value circuits that came after
+the tier (select, minmax, lookup, shift, count, array): their case tables, a third operand where
+the operation has one, their references (the big-integer models of tests/*_model.py), traces that
+replay each kernel's own sequence of products on the model integers, and path assertions that
+take every slot size from the plan drivers tests/sanitize/*_plan.cpp.
 """
 from __future__ import annotations
 
@@ -439,6 +445,8 @@ def _seed(family, name):
 @functools.lru_cache(maxsize=None)
 def inputs(family, name):
     """dict(ba, bb, A, B, n, nbits) of a case (model form), made once."""
+    if family in _WAVE_FAMILIES:  # select, minmax, lookup, shift: a third operand where there is one
+        return _WAVE_FAMILIES[family](name)
     if family == "gate":
         ba, bb = GATE_CASES[name]
         ns, npair = 8, 2
@@ -464,9 +472,11 @@ def inputs(family, name):
 
 
 def packed(family, name):
-    """The case's operands in the batch layout: (la, da, lb, db)."""
+    """The case's operands in the batch layout: (la, da, lb, db), then (lc, dc) where the case has
+    a third operand (select's condition: inputs()["C"], ["bc"])."""
     c = inputs(family, name)
-    return bm.pack(c["A"], c["ba"]) + bm.pack(c["B"], c["bb"])
+    out = bm.pack(c["A"], c["ba"]) + bm.pack(c["B"], c["bb"])
+    return out + bm.pack(c["C"], c["bc"]) if "C" in c else out
 
 
 def _frozen(l, d):
@@ -930,3 +940,1041 @@ def _check_dec_path_case(name):
     else:
         raise KeyError(name)
     return d
+
+
+# =============================================================================================
+# The wave-per-value circuits added after the tier: select, min / max, lookup, shift (kernels.hip).
+# All go through wave_mul<kQSmall = 10, 8>(U, nu, V, nv, Add, nadd, Dst): nout = max(nu + nv, nadd)
+# words, tile width W = ceil(nout / 64) up to 8, MULTI tiles past 512 words, U read in chunks of 10.
+# The traces below replay each kernel's own sequence of products on the model integers.
+import lookup_model as lm  # noqa: E402
+import select_model as sm  # noqa: E402
+import shift_model as shm  # noqa: E402
+
+LDS_WORDS = 10240  # a wave's share of a CU's LDS (circuit_host.h fits_cu_lds)
+
+
+def wob(b):
+    """words_of_bound: the words of a polynomial of degree b."""
+    return int(b) // 32 + 1
+
+
+def product_shape(nu, nv, nadd=0):
+    """wave_mul's own sizes: (nout, tile width W, tiles, uniform chunks of kQSmall words)."""
+    nout = max(nu + nv, nadd)
+    w = max(1, min(8, (nout + 63) // 64))
+    return nout, w, max(1, (nout + 64 * w - 1) // (64 * w)), (nu + 9) // 10
+
+
+def deg(p):
+    return p.bit_length() - 1
+
+
+def _reaches(vals, ob, bits=None):
+    """At every output bit some value has degree equal to the output bound."""
+    for i in (range(len(ob)) if bits is None else bits):
+        assert max(deg(v[i]) for v in vals) == int(ob[i]), (i, int(ob[i]))
+
+
+# ------------------------------------------------------------------ the plan drivers
+@functools.lru_cache(maxsize=None)
+def _plan_driver(name):
+    """tests/sanitize/<name>_plan.cpp, the planner header compiled alone into an ASan + UBSan
+    driver (as test_circuit_plans.py and its siblings build it), once per process."""
+    import os
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = os.path.join(root, "tests", "sanitize", "_build")
+    os.makedirs(out, exist_ok=True)
+    exe = os.path.join(out, f"{name}_plan_{os.getpid()}")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=all",
+                    os.path.join(root, "tests", "sanitize", f"{name}_plan.cpp"), "-o", exe],
+                   check=True, capture_output=True, timeout=300)
+    import atexit
+    atexit.register(lambda: os.path.exists(exe) and os.remove(exe))
+    return exe
+
+
+@functools.lru_cache(maxsize=None)
+def _plan(name, line):
+    """The driver's JSON rows for one case line given on stdin."""
+    import json
+    import os
+    import subprocess
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0",
+               UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([_plan_driver(name)], input=line + "\n", capture_output=True, text=True,
+                       timeout=120, env=env)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    return [json.loads(x) for x in r.stdout.splitlines()]
+
+
+def _ints(x):
+    return " ".join(str(int(v)) for v in x)
+
+
+def select_plan(cb, ba, bb):
+    """plan_select through tests/sanitize/circuit_plan.cpp."""
+    return _plan("circuit", f"select {len(ba)} {int(cb)} {_ints(ba)} {_ints(bb)}")[1]
+
+
+def minmax_plan(ba, bb):
+    """hm_minmax_batch's plan_borrow (chain = wb_L) through tests/sanitize/circuit_plan.cpp."""
+    return _plan("circuit", f"minmax {len(ba)} 0 {_ints(ba)} {_ints(bb)}")[1]
+
+
+def lookup_plan(k, ab, table):
+    """plan_lookup through tests/sanitize/lookup_plan.cpp (its first row; the driver's own closing
+    case follows)."""
+    t = np.asarray(table)
+    raw = np.ascontiguousarray(t.astype(t.dtype.newbyteorder("<"))).view(np.uint8).reshape(-1)
+    return _plan("lookup", f"{k} {t.dtype.itemsize} {_ints(ab[:k])} {raw.tobytes().hex()}")[0]
+
+
+SHIFT_CODES = {"shl": 18, "shr": 19, "rotl": 20, "rotr": 21}
+
+
+def shift_plan(op, signed, ba, bs):
+    """plan_shift through tests/sanitize/shift_plan.cpp (its first row)."""
+    L = shm.stages(len(ba))
+    return _plan("shift", f"{SHIFT_CODES[op]} {int(signed)} {len(ba)} {_ints(ba)} {_ints(bs[:L])}")[0]
+
+
+# ------------------------------------------------------------------ select
+def _per_bit_select():
+    i = np.arange(8)
+    return u32(64 * i + 63), u32(1000 - 97 * i)
+
+
+SELECT_CASES = {
+    # name: (condition bound, a bounds, b bounds)
+    "w1_edge": (1023, uniform(8, 1023), uniform(8, 1023)),
+    "w2_edge": (1023, uniform(8, 1055), uniform(8, 1055)),
+    "one_tile": (8191, uniform(8, 8191), uniform(8, 8191)),
+    "multi_tile": (8191, uniform(8, 8223), uniform(8, 8223)),
+    "chunks_10_11": (500, uniform(8, 319), uniform(8, 320)),
+    "chunks_20_21": (500, uniform(8, 639), uniform(8, 640)),
+    "lopsided": (9000, uniform(8, 40), uniform(8, 40)),
+    "lopsided_swapped": (40, uniform(8, 9000), uniform(8, 9000)),
+    "per_bit": (500,) + _per_bit_select(),
+}
+COND_SHIFT = 5  # the condition of value e < 8 is of kind (e + 5) mod 8
+
+
+def _bool_batch(polys, cb):
+    """A Ciphered<bool> batch in model form: bit 0 the polynomial, bits 1..7 null at bound 0."""
+    return [[p] + [0] * 7 for p in polys], u32([int(cb)] + [0] * 7)
+
+
+def _select_inputs(name):
+    cb, ba, bb = SELECT_CASES[name]
+    seed = _seed("select", name)
+    rng = np.random.default_rng(seed + 9)
+    A, B = operands(ba, 8, seed, 0), operands(bb, 8, seed + 1, 3)
+    C = [poly(KINDS[(e + COND_SHIFT) % 8], cb, rng) for e in range(8)]
+    # a FULL against b one below its bound, and the other way round: x_i keeps the wider bound
+    PA, PB = full_pair(ba, bb, 1, seed + 2)
+    QB, QA = full_pair(bb, ba, 1, seed + 3)
+    A, B, C = A + PA + QA, B + PB + QB, C + [_exact(rng, int(cb)), _exact(rng, int(cb))]
+    if name == "per_bit":
+        # b_i as long as both bounds allow and a_i = b_i + one word: x_i is one word, so under a
+        # UNIT or a one-word condition the product is shorter than the b_i it is added to
+        for c in (1, _exact(rng, 20)):
+            bv = [_exact(rng, int(min(x, y))) for x, y in zip(ba, bb)]
+            A.append([p ^ _exact(rng, 17) for p in bv])
+            B.append(bv)
+            C.append(c)
+    Cv, bc = _bool_batch(C, cb)
+    return dict(ba=u32(ba), bb=u32(bb), bc=bc, A=A, B=B, C=Cv, n=len(A), nbits=len(ba))
+
+
+@functools.lru_cache(maxsize=None)
+def select_reference(name):
+    """(out bounds, values, limbs, degree words) of select_model.select_circuit on the case."""
+    c = inputs("select", name)
+    ob = sm.select_bounds(c["bc"][0], c["ba"], c["bb"])
+    vals = [sm.select_circuit(cv[0], a, b) for cv, a, b in zip(c["C"], c["A"], c["B"])]
+    return (ob, vals) + _frozen(*bm.pack(vals, ob))
+
+
+def select_trace(c, a, b):
+    """Per bit of one value, as select_kernel runs it: wave_mul(X, nx, C, nc, Bb, nb, T) -- x_i is
+    the uniform operand, the condition the per-lane one, b_i is added."""
+    rows = []
+    for i, (x, y) in enumerate(zip(a, b)):
+        nx, nc, nb = words(x ^ y), words(c), words(y)
+        nout, w, tiles, chunks = product_shape(nx, nc, nb)
+        rows.append(dict(i=i, na=words(x), nb=nb, nx=nx, nc=nc, nout=nout, w=w, tiles=tiles,
+                         chunks=chunks, live=bool(nx and nc)))
+    return rows
+
+
+def check_select_path(name):
+    """The path each select case is named for, and that the case fills its bounds and its slots
+    (plan_select's, from the plan driver)."""
+    c = inputs("select", name)
+    cb = int(c["bc"][0])
+    tr = [select_trace(cv[0], a, b) for cv, a, b in zip(c["C"], c["A"], c["B"])]
+    rows = [r for t in tr for r in t]
+    live = [r for r in rows if r["live"]]
+    top = max(live, key=lambda r: r["nx"] + r["nc"])
+    nprod = top["nx"] + top["nc"]
+    if name == "w1_edge":
+        assert nprod == 64 and (top["w"], top["tiles"]) == (1, 1)
+    elif name == "w2_edge":
+        assert nprod == 65 and (top["w"], top["tiles"]) == (2, 1)
+    elif name == "one_tile":
+        assert nprod == 512 and (top["w"], top["tiles"]) == (8, 1)
+    elif name == "multi_tile":
+        assert nprod == 513 and (top["w"], top["tiles"]) == (8, 2)
+    elif name in ("chunks_10_11", "chunks_20_21"):
+        lo = 10 if name == "chunks_10_11" else 20
+        assert {lo, lo + 1} <= {r["nx"] for r in live}
+        assert {lo // 10, lo // 10 + 1} <= {r["chunks"] for r in live}
+    elif name == "lopsided":
+        assert max(r["nx"] for r in live) == 2 and max(r["nc"] for r in live) == 282
+    elif name == "lopsided_swapped":
+        assert max(r["nx"] for r in live) == 282 and (282 + 9) // 10 == 29
+        assert max(r["nc"] for r in live) == 2
+    elif name == "per_bit":
+        ca, cbb = c["ba"] // 64 + 1, c["bb"] // 64 + 1
+        assert len(set(ca.tolist())) == 8 and len(set(cbb.tolist())) == 8
+        for i in range(8):  # every bit's slot is filled by some value
+            assert max(t[i]["na"] for t in tr) == wob(c["ba"][i])
+            assert max(t[i]["nb"] for t in tr) == wob(c["bb"][i])
+        # the product shorter than what it is added to: nout = nadd
+        short = [r for r in live if r["nb"] > r["nx"] + r["nc"]]
+        assert {r["i"] for r in short} == set(range(1, 8))  # (bit 0's b_0 has two words itself)
+        assert all(r["nout"] == r["nb"] for r in short)
+    else:
+        raise KeyError(name)
+    # the condition's kinds over the values: NULL has a null product over nout = max(nx, nb)
+    # words, an exact copy of b_i; UNIT has nc = 1
+    kinds = [KINDS[(e + COND_SHIFT) % 8] for e in range(8)]
+    e0, e1 = kinds.index("NULL"), kinds.index("UNIT")
+    ob, vals, _, _ = select_reference(name)
+    assert all(r["nc"] == 0 and r["nout"] == max(r["nx"], r["nb"]) and not r["live"] for r in tr[e0])
+    assert vals[e0] == c["B"][e0] and any(r["nx"] > r["nb"] for r in tr[e0])
+    assert all(r["nc"] == 1 for r in tr[e1])
+    # fills: every output bound, and every slot of the plan to the last word its bound allows
+    _reaches(vals, ob)
+    p = select_plan(cb, c["ba"], c["bb"])
+    assert p["status"] == 0 and p["lds_per_wave"] <= LDS_WORDS
+    nc, na, nb, nx = (max(r[k] for r in rows) for k in ("nc", "na", "nb", "nx"))
+    assert nc == wob(cb) and 0 <= p["SC"] - nc <= 1
+    assert na == wob(c["ba"].max()) and 0 <= p["SA"] - na <= 1
+    assert nb == wob(c["bb"].max()) and 0 <= p["SB"] - nb <= 1
+    assert nx == max(na, nb) and 0 <= p["SX"] - nx <= 1
+    tcap = p["lds_per_wave"] - p["oT"]  # the product buffer: SC + SX + 2 words
+    assert tcap == p["SC"] + p["SX"] + 2 and nprod == nc + nx and nprod <= tcap
+    assert max(r["nout"] for r in rows) <= tcap
+    return dict(nprod=nprod, plan=p, rows=rows)
+
+
+# ------------------------------------------------------------------ min / max
+MINMAX_OWN = {
+    # name: (a bounds, b bounds, scheduled + random values, FULL / bound - 1 pairs)
+    "p2_one_tile": (uniform(8, 1632), uniform(8, 1632), 8, 2),
+    "p2_multi_tile": (uniform(8, 1636), uniform(8, 1636), 8, 2),
+    "null_borrow": (uniform(8, 255), uniform(8, 255), 0, 2),
+}
+MINMAX_CASES = tuple(BORROW_CASES) + tuple(MINMAX_OWN)
+
+
+def _minmax_inputs(name):
+    if name in BORROW_CASES:
+        c = dict(inputs("borrow", name))
+        if (c["ba"] != c["bb"]).all():
+            # full_pair's b_i, one below its bound, leaves p_i short wherever bb_i > ba_i; with
+            # no two bounds equal nothing cancels, and one all-FULL value takes w_n to its bound
+            rng = np.random.default_rng(_seed("minmax", name))
+            c["A"] = c["A"] + [[_exact(rng, int(b)) for b in c["ba"]]]
+            c["B"] = c["B"] + [[_exact(rng, int(b)) for b in c["bb"]]]
+            c["n"] += 1
+        return c
+    ba, bb, ns, npair = MINMAX_OWN[name]
+    seed = _seed("minmax", name)
+    A, B = batch(ba, bb, ns, npair, seed)
+    if name == "null_borrow":
+        # w_{i+1} = (a_i + 1) b_i + p_i w_i stays null when every b_i is null or every a_i is the
+        # unit: a = b bit for bit over {0, 1} (x_i null as well), then b null under a of every kind
+        pat = [[(v >> i) & 1 for i in range(8)] for v in (0x00, 0xFF, 0xA5)]
+        A = [list(p) for p in pat] + operands(ba, 3, seed + 6, 0) + A
+        B = [list(p) for p in pat] + [[0] * 8 for _ in range(3)] + B
+    return dict(ba=u32(ba), bb=u32(bb), A=A, B=B, n=len(A), nbits=len(ba))
+
+
+@functools.lru_cache(maxsize=None)
+def minmax_reference(name, op, signed=False):
+    """op "min" or "max": (out bounds, values, limbs, degree words) of select_model's circuits."""
+    c = inputs("minmax", name)
+    ob = sm.minmax_bounds(c["ba"], c["bb"])
+    f = sm.min_circuit if op == "min" else sm.max_circuit
+    vals = [f(a, b, signed) for a, b in zip(c["A"], c["B"])]
+    return (ob, vals) + _frozen(*bm.pack(vals, ob))
+
+
+def minmax_trace(a, b, is_max=False, signed=False):
+    """minmax_kernel's phase 2 on one value: wave_mul(X, nx, W, nw, is_max ? Ab : Bb, .., Wn) with
+    W = w_n, the last borrow of phase 1 (borrow_trace is phase 1)."""
+    w = sm.less_than(a, b, signed)
+    rows = []
+    for i, (x, y) in enumerate(zip(a, b)):
+        nx, nw, nadd = words(x ^ y), words(w), words(x if is_max else y)
+        nout, tw, tiles, chunks = product_shape(nx, nw, nadd)
+        rows.append(dict(i=i, nx=nx, nw=nw, nadd=nadd, nout=nout, w=tw, tiles=tiles,
+                         chunks=chunks, live=bool(nx and nw)))
+    return rows
+
+
+def check_minmax_path(name):
+    """Phase 2 of minmax_kernel (phase 1 is borrow_step: check_borrow_path) in plan_borrow's layout
+    with chain = wb_L: the product x_i w_n goes to a borrow buffer of cw words."""
+    c = inputs("minmax", name)
+    tr = [minmax_trace(a, b) for a, b in zip(c["A"], c["B"])]
+    rows = [r for t in tr for r in t]
+    live = [r for r in rows if r["live"]]
+    top = max(live, key=lambda r: r["nx"] + r["nw"])
+    nprod = top["nx"] + top["nw"]
+    if name == "p2_one_tile":
+        assert (top["nx"], top["nw"], nprod) == (52, 460, 512) and (top["w"], top["tiles"]) == (8, 1)
+    elif name == "p2_multi_tile":
+        assert (top["nx"], top["nw"], nprod) == (52, 461, 513) and (top["w"], top["tiles"]) == (8, 2)
+    elif name == "null_borrow":
+        null = [t for t in tr if all(r["nw"] == 0 for r in t)]
+        assert len(null) == 6
+        # ... x_i null too (three values) and x_i of every kind under the null borrow (three)
+        assert sum(all(r["nx"] == 0 for r in t) for t in null) >= 2
+        assert any(r["nx"] == 8 for t in null for r in t)
+        assert all(r["nout"] == max(r["nx"], r["nadd"]) and not r["live"] for t in null for r in t)
+        for op in ("min", "max"):  # min copies b, max copies a
+            _, vals, _, _ = minmax_reference(name, op)
+            src = c["B"] if op == "min" else c["A"]
+            assert vals[:6] == src[:6]
+    elif name == "u16_per_bit":
+        assert nprod > 512 and top["tiles"] == 2
+    elif name not in BORROW_CASES:
+        raise KeyError(name)
+    # fills.  Bit 0 with ba_0 = bb_0 cannot: w_n at its bound needs a_0 and b_0 both at theirs (the
+    # first borrow a_0 b_0 + b_0), and then the tops cancel in x_0: one below the bound there
+    ob, vals, _, _ = minmax_reference(name, "min")
+    rest = range(int(c["ba"][0] == c["bb"][0]), c["nbits"])
+    _reaches(vals, ob, rest)
+    _reaches(minmax_reference(name, "max")[1], ob, rest)
+    if c["ba"][0] == c["bb"][0]:
+        assert max(deg(v[0]) for v in vals) == int(ob[0]) - 1
+    p = minmax_plan(c["ba"], c["bb"])
+    assert p["status"] == 0 and p["lds_per_wave"] <= LDS_WORDS
+    chain = bm.borrow_bounds(c["ba"], c["bb"], c["nbits"])[-1]
+    assert p["chain"] == chain and max(r["nw"] for r in rows) == wob(chain)
+    nx = max(r["nx"] for r in rows)
+    assert nx == wob(max(c["ba"].max(), c["bb"].max())) and 0 <= p["SX"] - nx <= 1
+    # the borrow buffer holds the widest product and is filled to the last word the bounds allow
+    assert nprod == nx + wob(chain) and p["cw"] - 2 - nprod == p["SX"] - nx
+    assert max(r["nout"] for r in rows) <= p["cw"]
+    return dict(nprod=nprod, plan=p, rows=rows)
+
+
+# ------------------------------------------------------------------ lookup
+def _lk(k, ab, nbits=8, dtype=np.uint8):
+    ab = list(ab) + [63] * (nbits - len(ab))  # the bits above the index are not read
+    return dict(k=k, ab=u32(ab), dtype=np.dtype(dtype))
+
+
+LOOKUP_CASES = {
+    "w1_edge": _lk(2, [1023, 1023]),
+    "w2_edge": _lk(2, [1023, 1055]),
+    "one_tile": _lk(8, [2040] * 8),
+    "multi_tile": _lk(8, [2040] * 7 + [2072]),
+    "chunks_319": _lk(4, [319] * 4),
+    "chunks_320": _lk(4, [320] * 4),
+    "chunks_639": _lk(4, [639] * 4),
+    "chunks_640": _lk(4, [640] * 4),
+    "odd_split_per_bit": _lk(5, [63 + 97 * i for i in range(5)], nbits=16),
+    "wide_out": _lk(3, [700] * 3, dtype=np.uint32),
+}
+LOOKUP_TABLES = ("all", "top", "random")
+
+
+def lookup_table(name, which):
+    """all: t[0] = 1 (all output bits of t[0] for wide_out, so that every one of its 32 bits has an
+    accumulator), every ANF coefficient set; top: t[2^k - 1] alone, the top monomial only; random:
+    seeded."""
+    spec = LOOKUP_CASES[name]
+    E, dt = 1 << spec["k"], spec["dtype"]
+    t = np.zeros(E, dtype=dt)
+    one = np.iinfo(dt).max if name == "wide_out" else 1
+    if which == "all":
+        t[0] = one
+    elif which == "top":
+        t[E - 1] = one
+    else:
+        rng = np.random.default_rng(_seed("lookup", name) + 77)
+        t = rng.integers(0, np.iinfo(dt).max, size=E, dtype=dt, endpoint=True)
+    t.setflags(write=False)
+    return t
+
+
+def _lookup_inputs(name):
+    spec = LOOKUP_CASES[name]
+    seed = _seed("lookup", name)
+    rng = np.random.default_rng(seed + 3)
+    A = operands(spec["ab"], 8, seed, 0)
+    A += [[_exact(rng, int(b)) for b in spec["ab"]] for _ in range(2)]  # products never cancel
+    return dict(ba=spec["ab"], bb=spec["ab"], A=A, B=A, n=len(A), nbits=len(spec["ab"]), k=spec["k"])
+
+
+@functools.lru_cache(maxsize=None)
+def _model_monomials(name):
+    c = inputs("lookup", name)
+    return [lm.monomials(a, c["k"]) for a in c["A"]]
+
+
+@functools.lru_cache(maxsize=None)
+def lookup_reference(name, which):
+    """(out bounds, values, limbs, degree words): lookup_model's circuit, out_j = the XOR of its
+    monomials (lookup_model.monomials, made once per case) over the table's coefficient masks
+    (lookup_model.moebius)."""
+    c = inputs("lookup", name)
+    t = lookup_table(name, which)
+    ob = lm.lookup_bounds(c["ba"], t)
+    vals = []
+    for M in _model_monomials(name):
+        out = []
+        for f in lm.moebius(t):
+            p = 0
+            for S, on in enumerate(f):
+                if on:
+                    p ^= M[S]
+            out.append(p)
+        vals.append(out)
+    return (ob, vals) + _frozen(*bm.pack(vals, ob))
+
+
+def lookup_trace(a, k, masks, need):
+    """lookup_kernel on one value: the monomials of the low kl and the high kh index bits by
+    doubling on the top bit (M[s | 1 << i] = a_i M[s], a_i uniform, only those in the plan's need
+    mask), then per output bit the accumulate P <- MH[t] I_jt + P.  Returns (mono: id -> words,
+    dbl: the doubling products' (id, nb, nm), acc: the accumulate products' dicts, out)."""
+    kl = (k + 1) // 2
+    kh = k - kl
+    M = {0: 1, 16: 1}
+    dbl = []
+    for h, kk, base in ((0, kl, 0), (16, kh, kl)):
+        for i in range(kk):
+            M[h + (1 << i)] = a[base + i]
+        for i in range(1, kk):
+            for s in range(1, 1 << i):
+                mid = h + (1 << i) + s
+                if not (need >> mid) & 1:
+                    continue
+                u, v = M[h + (1 << i)], M[h + s]
+                M[mid] = model.clmul_fast(u, v)
+                dbl.append((mid, words(u), words(v)))
+    acc, out = [], []
+    for j, mask in enumerate(masks):
+        p = 0
+        for t in range(1 << kh):
+            m = (mask >> (t << kl)) & ((1 << (1 << kl)) - 1)
+            if not m:
+                continue
+            inner = 0
+            for s in range(1 << kl):
+                if (m >> s) & 1:
+                    inner ^= M[s]
+            if t == 0:
+                p = inner
+                continue
+            nh = words(M[16 + t])
+            if not nh or not inner:
+                continue
+            nout, w, tiles, chunks = product_shape(nh, words(inner), words(p))
+            acc.append(dict(j=j, t=t, nh=nh, ni=words(inner), np=words(p), nout=nout, w=w,
+                            tiles=tiles, chunks=chunks))
+            p ^= model.clmul_fast(M[16 + t], inner)
+        out.append(p)
+    return {s: words(p) for s, p in M.items()}, dbl, acc, out
+
+
+@functools.lru_cache(maxsize=None)
+def lookup_traces(name, which):
+    c = inputs("lookup", name)
+    t = lookup_table(name, which)
+    p = lookup_plan(c["k"], c["ba"], t)
+    assert p["status"] == 0, p
+    masks = lm.coefficient_masks(t)
+    assert [int(x, 16) for x in p["masks"]] == masks
+    return p, [lookup_trace(a, c["k"], masks, p["need"]) for a in c["A"]]
+
+
+def check_lookup_path(name):
+    """The path each lookup case is named for, on the "all" table (every monomial in use) unless
+    noted; plan_lookup's slots (off[], cI, cP) from the plan driver, each filled."""
+    c = inputs("lookup", name)
+    k, ab = c["k"], [int(x) for x in c["ba"][:c["k"]]]
+    kl = (k + 1) // 2
+    kh = k - kl
+    p, tr = lookup_traces(name, "all")
+    assert (p["kl"], p["kh"]) == (kl, kh) and p["lds_per_wave"] <= LDS_WORDS
+    acc = [r for _, _, a, _ in tr for r in a]
+    dbl = [r for _, d, _, _ in tr for r in d]
+    top = max(acc, key=lambda r: r["nh"] + r["ni"])
+    nprod = top["nh"] + top["ni"]
+    if name == "w1_edge":
+        assert (top["nh"], top["ni"]) == (32, 32) and (top["w"], top["tiles"]) == (1, 1)
+    elif name == "w2_edge":
+        assert (top["nh"], top["ni"]) == (33, 32) and (top["w"], top["tiles"]) == (2, 1)
+    elif name == "one_tile":
+        assert (top["nh"], top["ni"]) == (256, 256) and (top["w"], top["tiles"]) == (8, 1)
+    elif name == "multi_tile":
+        assert (top["nh"], top["ni"]) == (257, 256) and (top["w"], top["tiles"]) == (8, 2)
+    elif name.startswith("chunks_"):
+        nu = {"chunks_319": 10, "chunks_320": 11, "chunks_639": 20, "chunks_640": 21}[name]
+        assert max(r[1] for r in dbl) == nu and (nu + 9) // 10 == {10: 1, 11: 2, 20: 2, 21: 3}[nu]
+    elif name == "odd_split_per_bit":
+        assert (kl, kh) == (3, 2)
+        sizes = [b - a for a, b in zip(sorted(set(p["off"]))[1:], sorted(set(p["off"]))[2:])]
+        assert len(set(sizes)) >= 6  # distinct slot sizes
+        # the `need` mask: all 8 + 4 monomials under the all and the random table; under the top
+        # table only each half's top monomial and the chain it is formed from (s without its top
+        # bit), so the doubling's `continue` is taken
+        pr, pt = lookup_traces(name, "random")[0], lookup_traces(name, "top")[0]
+        assert pr["need"] == p["need"] == 0x000F00FF
+        assert pt["need"] == 0x000B008B, hex(pt["need"])  # low 7 <- 3 <- 1 <- 0, high 3 <- 1 <- 0
+    elif name == "wide_out":
+        assert len(tr[-1][3]) == 32 and {r["j"] for r in acc} == set(range(32))
+        assert all(sum(1 for r in a if r["j"] == j) == (1 << kh) - 1 for j in range(32)
+                   for a in (tr[-1][2],))  # P / Pn exchanged an odd number of times per bit
+    else:
+        raise KeyError(name)
+    # the index bits' kinds: a NULL bit nulls every monomial above it (skipped on `!nh` or on a
+    # null inner sum), a UNIT bit makes its product a copy
+    assert any(w == 0 for mono, _, _, _ in tr[:8] for s, w in mono.items() if s not in (0, 16))
+    assert any(nb == 1 or nm == 1 for _, nb, nm in dbl) or k == 2
+    # fills: the output bounds, then every slot of the plan
+    for which in ("all", "top"):
+        ob, vals, _, _ = lookup_reference(name, which)
+        used = [j for j in range(len(ob)) if any(lm.moebius(lookup_table(name, which))[j])]
+        _reaches(vals, ob, used)
+    offs = sorted(set(p["off"]) | {p["oI"]})
+    for s in range(1, 32):
+        if not (p["need"] >> s) & 1 or s in (0, 16):
+            continue
+        bits = [(0 if s < 16 else kl) + i for i in range(4) if ((s & 15) >> i) & 1]
+        if s < 16 and not all(i < kl for i in bits) or s >= 16 and not all(i < k for i in bits):
+            continue
+        bound = sum(ab[i] for i in bits)
+        slot = offs[offs.index(p["off"][s]) + 1] - p["off"][s]
+        got = max(mono.get(s, 0) for mono, _, _, _ in tr)
+        assert got == wob(bound) and got <= slot <= got + 3, (s, got, slot)
+    cI = max(r["ni"] for r in acc)
+    cH = max(r["nh"] for r in acc)
+    assert cI == p["cI"] == wob(sum(ab[:kl])) and cH == wob(sum(ab[kl:]))
+    assert p["oP"] - p["oI"] >= cI and nprod == cI + cH and 0 <= p["cP"] - 2 - nprod <= 1
+    assert p["lds_per_wave"] == p["oP"] + 2 * p["cP"]
+    return dict(nprod=nprod, plan=p)
+
+
+# ------------------------------------------------------------------ shift
+def _sh(bs, ba, params=PARAMS):
+    bs = list(bs) + [0] * (8 - len(bs))  # the amount is a u8 batch; its low log2 n bits are read
+    return dict(bs=u32(bs), ba=u32(ba), params=params)
+
+
+SHIFT_CASES = {
+    "w1_edge": _sh([255] * 3, [1279] * 8),
+    "w2_edge": _sh([255] * 3, [1311] * 8),
+    "one_tile": _sh([255] * 3, [15615] * 8),
+    "multi_tile": _sh([255] * 3, [15647] * 8),
+    "chunks": _sh([319, 320, 639], [200 + 7 * i for i in range(8)]),
+    # (64 i + 63 up to bit 4, then down again: ascending bounds alone would give every SHR slot
+    # the same suffix maximum)
+    "per_bit": _sh([63, 700, 320], [63, 191, 319, 447, 511, 383, 255, 127]),
+    "stage_subsets": _sh([255] * 3, [300 + 5 * i for i in range(8)]),
+    "u32_headline_shape": _sh([256] * 5, [256] * 32, DEC_PARAMS),
+}
+AMOUNT_SHIFT = 5  # amount bit t of value e < 8 is of kind (e + t + 5) mod 8
+
+
+def _shift_inputs(name):
+    spec = SHIFT_CASES[name]
+    ba, bs = spec["ba"], spec["bs"]
+    n, L = len(ba), shm.stages(len(ba))
+    seed = _seed("shift", name)
+    rng = np.random.default_rng(seed + 4)
+    full_s = lambda: [_exact(rng, int(bs[t])) if t < L else 0 for t in range(8)]  # noqa: E731
+    if name == "stage_subsets":  # value e: s_t null iff bit t of e is clear; FULL otherwise
+        A = [[_exact(rng, int(b)) for b in ba] for _ in range(8)]
+        S = [[_exact(rng, int(bs[t])) if (e >> t) & 1 else 0 for t in range(L)] + [0] * (8 - L)
+             for e in range(8)]
+    else:
+        A = operands(ba, 8, seed, 0)
+        S = [[poly(kind_of(e, t, AMOUNT_SHIFT), bs[t], rng) if t < L else 0 for t in range(8)]
+             for e in range(8)]
+    if len(set(ba.tolist())) == 1:
+        # equal tops cancel: an output's top coefficient is the parity of the FULL bits among its
+        # sources, so one bit FULL and the others one below -- bit 0 (shl, the rotates), the top
+        # bit (shr) and the one below it (the arithmetic shr, whose top bit stays a_{n-1} itself)
+        for hot in (0, n - 1, n - 2):
+            A.append([_exact(rng, int(b) - (i != hot)) for i, b in enumerate(ba)])
+            S.append(full_s())
+    else:
+        for _ in range(2):
+            A.append([_exact(rng, int(b)) for b in ba])
+            S.append(full_s())
+    return dict(ba=ba, bb=bs, A=A, B=S, n=len(A), nbits=n, L=L, params=spec["params"])
+
+
+@functools.lru_cache(maxsize=None)
+def shift_reference(name, op, signed=False):
+    """(out bounds, values, limbs, degree words) of shift_model.shift_circuit (stages ascending)."""
+    c = inputs("shift", name)
+    ob = shm.shift_bounds(op, c["ba"], c["bb"])
+    vals = [shm.shift_circuit(op, a, s, signed) for a, s in zip(c["A"], c["B"])]
+    return (ob, vals) + _frozen(*bm.pack(vals, ob))
+
+
+def shift_trace(op, signed, a, s):
+    """shift_kernel on one value: the stages from the widest step down to `last`, the lowest t
+    whose s_t is not null, null stages skipped; per product wave_mul(S, ns, V, nv, xi, ni, T) with
+    V = x_i + x_src (x_i alone where the source is null).  Every stage but `last` rewrites the
+    slots; a rotate saves the 2^t bits that wrap first.  Returns (last, rows, slot: the widest
+    content of each slot, saved: t -> the widest saved bit, out)."""
+    n = len(a)
+    L = shm.stages(n)
+    x = list(a)
+    slot = [words(p) for p in x]
+    saved, rows = {}, []
+    live = [t for t in range(L) if s[t]]
+    last = live[0] if live else -1
+    if last < 0:
+        return last, rows, slot, saved, x
+    for t in range(L - 1, last - 1, -1):
+        if not s[t]:
+            continue
+        k, fin = 1 << t, t == last
+        if op in ("rotl", "rotr") and not fin:
+            wrap = x[n - k:] if op == "rotl" else x[:k]
+            saved[t] = max(words(p) for p in wrap)
+        y = []
+        for i in range(n):
+            j = shm.source(op, n, k, i, signed)
+            v = x[i] ^ (x[j] if j is not None else 0)
+            nout, w, tiles, chunks = product_shape(words(s[t]), words(v), words(x[i]))
+            rows.append(dict(t=t, i=i, fin=fin, ns=words(s[t]), nv=words(v), ni=words(x[i]),
+                             nout=nout, w=w, tiles=tiles, chunks=chunks))
+            y.append(x[i] ^ model.clmul_fast(s[t], v))
+        x = y
+        if not fin:
+            slot = [max(q, words(p)) for q, p in zip(slot, x)]
+    return last, rows, slot, saved, x
+
+
+@functools.lru_cache(maxsize=None)
+def shift_traces(name, op, signed=False):
+    c = inputs("shift", name)
+    return [shift_trace(op, signed, a, s) for a, s in zip(c["A"], c["B"])]
+
+
+def check_shift_path(name, op, signed=False):
+    """The path each shift case is named for, in one mode; plan_shift's slots (off[], the X / T
+    buffers, the rotates' save area sv[t]) from the plan driver, each filled as far as a value in
+    LDS can fill it (the final stage's products go from T to the output, not to a slot)."""
+    c = inputs("shift", name)
+    n, L = c["nbits"], c["L"]
+    ba, bs = [int(b) for b in c["ba"]], [int(b) for b in c["bb"][:L]]
+    tr = shift_traces(name, op, signed)
+    rows = [r for _, rs, _, _, _ in tr for r in rs]
+    fin0 = [r for r in rows if r["fin"] and r["t"] == 0]
+    top = max(fin0, key=lambda r: r["ns"] + r["nv"])
+    nprod = top["ns"] + top["nv"]
+    edge = {"w1_edge": (8, 56, 1, 1), "w2_edge": (8, 57, 2, 1), "one_tile": (8, 504, 8, 1),
+            "multi_tile": (8, 505, 8, 2)}
+    if name in edge:
+        assert (top["ns"], top["nv"], top["w"], top["tiles"]) == edge[name]
+    elif name == "chunks":
+        assert {t: max(r["ns"] for r in rows if r["t"] == t) for t in range(3)} == {0: 10, 1: 11, 2: 20}
+        assert {r["chunks"] for r in rows} >= {1, 2}
+    elif name == "stage_subsets":
+        assert [t[0] for t in tr[:8]] == [-1, 0, 1, 0, 2, 0, 1, 0]
+        assert {r["t"] for r in tr[5][1]} == {0, 2}  # the middle stage skipped
+        assert tr[0][4] == c["A"][0]  # the null amount: the copy-out
+    elif name == "u32_headline_shape":
+        assert (n, L) == (32, 5) and {r["t"] for r in rows} == set(range(5))
+    elif name != "per_bit":
+        raise KeyError(name)
+    ob, vals, _, _ = shift_reference(name, op, signed)
+    if signed:
+        # an arithmetic shr keeps its top bit, out_{n-1} = a_{n-1}, and bit j takes a_{n-1} under
+        # the sum of j + 1 amount indicators, whose common top term cancels when j + 1 is even: the
+        # bound is out of reach there unless a bit below the top one is as wide
+        assert all(v[n - 1] == a[n - 1] for v, a in zip(vals, c["A"]))
+        _reaches(vals, ob, [j for j in range(n - 1) if j % 2 == 0 or max(ba[j:n - 1]) >= ba[n - 1]])
+    else:
+        _reaches(vals, ob)
+    p = shift_plan(op, signed, ba, bs)
+    assert p["status"] == 0 and p["lds_per_wave"] <= LDS_WORDS and p["bounds"] == ob.tolist()
+    sizes = [b - a for a, b in zip(p["off"], p["off"][1:] + [p["cV"]])]
+    widest = p["oT"] - p["oX"]
+    assert widest == p["oS"] - p["oT"] == max(sizes)
+    # T and X: the widest product (the final stage's: its factors' words, one more than the
+    # result's when the top word stays empty) reaches the last word the widest bound allows
+    assert wob(max(ob)) <= max(r["nout"] for r in rows) <= wob(max(ob)) + 1 <= widest
+    assert widest - wob(max(ob)) <= 2
+    # a slot holds what the stages above stage 0 leave in it (the last stage's products go from T
+    # to the output): the bounds through those stages, bit by bit
+    reach = list(ba)
+    for t in range(L - 1, 0, -1):
+        src = [shm.source(op, n, 1 << t, i, signed) for i in range(n)]
+        reach = [b if j == i else bs[t] + max(b, reach[j] if j is not None else 0)
+                 for i, (b, j) in enumerate(zip(reach, src))]
+    content = [max(t[2][i] for t in tr) for i in range(n)]
+    assert max(content) == wob(max(reach))
+    for i in range(n):
+        assert content[i] <= wob(reach[i]) <= sizes[i], (i, content, reach, sizes)
+        # (under equal bounds, and under the arithmetic shr's repeated top bit, tops cancel by
+        # parity at some bits; the u8 cases' one-FULL-bit values avoid it at every bit)
+        if not signed and (n == 8 or len(set(ba)) == n):
+            assert content[i] == wob(reach[i]), (i, content, reach)
+    if name == "per_bit" and op in ("shl", "shr"):
+        assert len(set(sizes)) >= 4  # prefix (shl) / suffix (shr) maxima: per-bit slots
+        assert sizes == sorted(sizes, reverse=(op == "shr"))
+    if name == "u32_headline_shape":
+        assert sizes == [sizes[0]] * 32 and ob.tolist() == [1536] * 32
+    if op in ("rotl", "rotr"):
+        for t in range(1, L):  # stage t's save area: the amount bounds above t plus the widest a
+            got = max(tr_[3].get(t, 0) for tr_ in tr)
+            full = wob(sum(bs[t + 1:]) + max(ba))
+            assert got <= full and 0 <= p["sv"][t] - 1 - full <= 1, (t, got)
+            if len(set(ba)) == 1:  # (per-bit bounds: the bits that wrap need not be the widest)
+                assert got == full, (t, got)
+        assert p["oV"] - p["oS"] == max((1 << t) * p["sv"][t] for t in range(L))
+    return dict(nprod=nprod, plan=p)
+
+
+# ------------------------------------------------------------------ counts and runs
+import array_model as am  # noqa: E402
+import bitcount_model as bcm  # noqa: E402
+
+SHARE_WORDS = 2560  # a wave's slice for the bit counts and the array circuits (bitcount_host.h)
+
+
+def _bits8(b, **at):
+    v = [b] * 8
+    for i, x in at.items():
+        v[int(i[1:])] = x
+    return u32(v)
+
+
+COUNT_OPS = tuple(bcm.OPS)
+COUNT_CASES = {
+    # name: (a bounds, the ops run)
+    "w1_edge": (_bits8(255), COUNT_OPS),
+    "w2_edge_top": (_bits8(255, b7=287), COUNT_OPS),
+    "w2_edge_low": (_bits8(255, b0=287), COUNT_OPS),  # (bit 0: the last literal of a leading run)
+    "chunks_319": (_bits8(319), COUNT_OPS),
+    "chunks_320": (_bits8(320), COUNT_OPS),
+    # (at 2040 the last running product is 64 + 447 = 511 words: 2047 is the bound whose product
+    # has 512; the planner takes the counts there and refuses the runs)
+    "one_tile": (_bits8(2047), COUNT_OPS[:2]),
+    "multi_tile": (_bits8(2047, b7=2079), COUNT_OPS[:2]),
+}
+
+
+def _count_inputs(name):
+    ba, _ = COUNT_CASES[name]
+    seed = _seed("count", name)
+    rng = np.random.default_rng(seed + 1)
+    A = operands(ba, 8, seed, 0)
+    # equal tops cancel by parity in a symmetric sum: all FULL reaches e_8 (and, with one wider
+    # bit, every e_{2^k}); seven FULL and bit 3 one below reach e_1, e_2, e_4 under equal bounds
+    A.append([_exact(rng, int(b)) for b in ba])
+    A.append([_exact(rng, int(b) - (i == 3)) for i, b in enumerate(ba)])
+    return dict(ba=ba, bb=ba, A=A, B=A, n=len(A), nbits=len(ba))
+
+
+@functools.lru_cache(maxsize=None)
+def count_reference(name, op):
+    """(out bounds, values, limbs, degree words) of bitcount_model.circuit."""
+    c = inputs("count", name)
+    ob = bcm.bitcount_bounds(op, c["ba"])
+    vals = [bcm.circuit(op, a) for a in c["A"]]
+    return (ob, vals) + _frozen(*bm.pack(vals, ob))
+
+
+def count_plan(op, ba):
+    """plan_bitcount through tests/sanitize/bitcount_plan.cpp (its first row)."""
+    return _plan("bitcount", f"{bcm.CODES[op]} {len(ba)} {_ints(ba)}")[0]
+
+
+def count_trace(a, zeros):
+    """bitcount_kernel on one value: E_j <- E_j + u_i E_{j-1} over the slots E_1 .. E_J (pruned by
+    bitcount_needed, formed in T), and past slot J the running product of all literals in D / Dn,
+    wave_mul(U, nu, P, np, ..) with the literal uniform.  Returns (the running products' (i, nu,
+    np), the slot products' (i, j, nu, np, ne), the widest content of each slot, out)."""
+    n = len(a)
+    top = 1 << (n.bit_length() - 1)
+    J = n // 2 if top == n and n >= 2 else top
+    diag = J < top
+    E, D = [1] + [0] * J, 0
+    emax, drows, erows = [0] * (J + 1), [], []
+    for i in range(1, n + 1):
+        u = a[i - 1] ^ 1 if zeros else a[i - 1]
+        if diag and i > J:
+            P = E[J] if i == J + 1 else D
+            if u and P:
+                drows.append((i, words(u), words(P)))
+            D = model.clmul_fast(u, P) if u and P else 0
+        if not u:
+            continue
+        for j in range(min(i, J), 1, -1):
+            if not bcm.needed(n, i, j) or not E[j - 1]:
+                continue
+            erows.append((i, j, words(u), words(E[j - 1]), words(E[j])))
+            E[j] ^= model.clmul_fast(u, E[j - 1])
+        E[1] ^= u
+        emax = [max(m, words(p)) for m, p in zip(emax, E)]
+    out = [E[1 << k] if 1 << k <= J else (D if diag and 1 << k == n else 0)
+           for k in range(bcm.OUT_BITS)]
+    return drows, erows, emax, out
+
+
+def run_trace(a, zeros, leading):
+    """bitrun_kernel on one value: t_j = t_{j-1} v_j in D / Dn, wave_mul(U, nu, D, np, ..), XORed
+    into the accumulator of every output bit k with 2^k | j; a null t_j ends the chain."""
+    n = len(a)
+    v = [x ^ 1 for x in a] if zeros else list(a)
+    if leading:
+        v = v[::-1]
+    K = n.bit_length()
+    acc, rows, t = [0] * K, [], 0
+    for j in range(1, n + 1):
+        if j > 1 and not t:
+            continue
+        u = v[j - 1]
+        if j == 1:
+            t = u
+        elif u:
+            rows.append((j, words(u), words(t)))
+            t = model.clmul_fast(u, t)
+        else:
+            t = 0
+        if t:
+            for k in range(K):
+                if j & ((1 << k) - 1):
+                    break
+                acc[k] ^= t
+    return rows, acc + [0] * (bcm.OUT_BITS - K)
+
+
+@functools.lru_cache(maxsize=None)
+def count_traces(name, op):
+    run, zeros, leading = bcm.OPS[op]
+    c = inputs("count", name)
+    return [run_trace(a, zeros, leading) if run else count_trace(a, zeros) for a in c["A"]]
+
+
+def check_count_path(name, op):
+    """The path each count case is named for, in one op; plan_bitcount's buffers (the running
+    product's D / Dn of cD words, the slots E_j or the runs' accumulators at off[]) from the plan
+    driver, the output ones filled to the last word their bounds allow."""
+    run, zeros, leading = bcm.OPS[op]
+    c = inputs("count", name)
+    ba = [int(b) for b in c["ba"]]
+    tr = count_traces(name, op)
+    chain = [r for t in tr for r in t[0]]  # the products in D / Dn: (position, nu, np)
+    top = max(chain, key=lambda r: (r[1] + r[2], r[1]))
+    nprod = top[1] + top[2]
+    _, w, tiles, _ = product_shape(top[1], top[2])
+    wide_last = (name == "w2_edge_top") != leading  # is the wide bit the chain's last literal?
+    if name == "w1_edge":
+        assert top[1:] == (8, 56) and (nprod, w, tiles) == (64, 1, 1) and top[0] == 8
+    elif name in ("w2_edge_top", "w2_edge_low"):
+        assert top[1:] == ((9, 56) if wide_last else (8, 57)) and (nprod, w) == (65, 2) and top[0] == 8
+    elif name in ("chunks_319", "chunks_320"):
+        nu = 10 if name == "chunks_319" else 11
+        assert max(r[1] for r in chain) == nu and (nu + 9) // 10 == nu - 9
+    elif name == "one_tile":
+        assert top[1:] == (64, 448) and (nprod, w, tiles) == (512, 8, 1)
+    elif name == "multi_tile":
+        assert top[1:] == (65, 448) and (nprod, w, tiles) == (513, 8, 2)
+    else:
+        raise KeyError(name)
+    ob, vals, _, _ = count_reference(name, op)
+    live = [k for k in range(bcm.OUT_BITS) if 1 << k <= len(ba)]
+    _reaches(vals, ob, live)
+    assert all(v[k] == 0 for v in vals for k in range(bcm.OUT_BITS) if k not in live)
+    p = count_plan(op, ba)
+    assert p["status"] == 0 and p["lds_per_wave"] <= SHARE_WORDS and p["bounds"] == ob.tolist()
+    assert nprod <= p["cD"] and p["cD"] - nprod <= 3  # even(sum / 32 + 2) words for sum / 32 + 1
+    ends = p["off"][1:p["J"] + 1] + [p["lds_per_wave"] - p["oE"]] if not run else \
+        p["off"][:p["K"]] + [p["lds_per_wave"] - p["oE"]]
+    sizes = [b - a for a, b in zip(ends, ends[1:])]
+    if run:
+        for k in range(p["K"]):
+            assert max(words(v[k]) for v in vals) == wob(ob[k]) <= sizes[k] <= wob(ob[k]) + 2
+    else:
+        assert p["J"] == 4 and p["diag"] == 1
+        sums = [sum(sorted(ba, reverse=True)[:j]) for j in range(p["J"] + 1)]
+        emax = [max(t[2][j] for t in tr) for j in range(p["J"] + 1)]
+        for j in range(1, p["J"] + 1):
+            assert emax[j] <= wob(sums[j]) <= sizes[j - 1] <= wob(sums[j]) + 2, (j, emax, sizes)
+            if j & (j - 1) == 0:  # an output's slot
+                assert emax[j] == wob(sums[j])
+        # T holds the widest slot product, u_i E_{J-1} + E_J
+        tmax = max(max(r[2] + r[3], r[4]) for t in tr for r in t[1])
+        assert tmax <= p["oD"] - p["oT"] and p["oD"] - p["oT"] - tmax <= 3
+    return dict(nprod=nprod, plan=p)
+
+
+# ------------------------------------------------------------------ array read and write
+def _arr(count, ba, bx=None, bs=255):
+    k = am.index_bits(count)
+    return dict(count=count, ba=u32(ba), bx=u32(ba if bx is None else bx),
+                bs=u32([bs] * k + [0] * (8 - k)))
+
+
+ARRAY_CASES = {
+    "w1_edge": _arr(4, [1535] * 8),
+    "w2_edge": _arr(4, [1567] * 8),
+    "count5_per_bit": _arr(5, [63 + 97 * i for i in range(8)], [700 - 83 * i for i in range(8)]),
+}
+INDEX_SHIFT, VALUE_SHIFT = 5, 6
+
+
+def _array_inputs(name):
+    """A: the array batch, count consecutive values per array; B: the index batch (u8, its low k
+    bits read); C: the written value."""
+    spec = ARRAY_CASES[name]
+    count, ba, bx, bs = spec["count"], spec["ba"], spec["bx"], spec["bs"]
+    k = am.index_bits(count)
+    seed = _seed("array", name)
+    rng = np.random.default_rng(seed + 2)
+    els = [operands(ba, 8, seed + 10 + v, v) for v in range(count)]  # element v of arrays 0 .. 7
+    arrs = [[els[v][e] for v in range(count)] for e in range(8)]
+    S = [[poly(kind_of(e, t, INDEX_SHIFT), bs[t], rng) if t < k else 0 for t in range(8)]
+         for e in range(8)]
+    X = operands(bx, 8, seed + 3, VALUE_SHIFT)
+    # the read's top coefficient is the parity of the elements at their bound: one FULL element
+    # and the others one below, x FULL; then every element FULL under an x one below its bound
+    full = lambda bnd, d=0: [_exact(rng, max(int(b) - d, 0)) for b in bnd]  # noqa: E731
+    arrs.append([full(ba, int(v != 0)) for v in range(count)])
+    arrs.append([full(ba) for v in range(count)])
+    X += [full(bx), full(bx, 1)]
+    S += [[_exact(rng, int(bs[t])) if t < k else 0 for t in range(8)] for _ in range(2)]
+    flat = [el for arr in arrs for el in arr]
+    return dict(ba=ba, bb=bs, bc=bx, A=flat, B=S, C=X, arrays=arrs, n=len(S), nbits=len(ba),
+                count=count, k=k)
+
+
+@functools.lru_cache(maxsize=None)
+def array_reference(name, what):
+    """what "read" or "write": (out bounds, values, limbs, degree words) of array_model's circuits
+    (the write's values: the output array batch, count elements per array)."""
+    c = inputs("array", name)
+    if what == "read":
+        ob = am.read_bounds(c["ba"], c["count"], c["bb"])
+        vals = [am.circuit_read(arr, s) for arr, s in zip(c["arrays"], c["B"])]
+    else:
+        ob = am.write_bounds(c["ba"], c["bc"], c["count"], c["bb"])
+        vals = [el for arr, s, x in zip(c["arrays"], c["B"], c["C"])
+                for el in am.circuit_write(arr, s, x)]
+    return (ob, vals) + _frozen(*bm.pack(vals, ob))
+
+
+def array_plan(what, count, ba, bs, bx=None):
+    """plan_array_read / plan_array_write through tests/sanitize/array_plan.cpp (its first row)."""
+    k = am.index_bits(count)
+    mid = f" {_ints(bx)}" if what == "write" else ""
+    return _plan("array", f"{am.CODES[what]} {len(ba)} {count} {_ints(ba)}{mid} {_ints(bs[:k])}")[0]
+
+
+def read_trace(arr, s):
+    """array_read_kernel on one array: per output bit the multiplexer tree, a level-t join as
+    wave_mul(s_t, ns, V, nv, Add, nadd, ..) with V = L + R and Add = L (under the last element with
+    nothing beside it V = Add = the node); a null s_t or V skips the product.  Rows (j, t, ns,
+    nv, nadd); the widest node per level."""
+    k = am.index_bits(len(arr))
+    rows, lvl = [], [0] * (k + 1)
+    for j in range(len(arr[0])):
+        level = [el[j] for el in arr]
+        for t in range(k):
+            lvl[t] = max([lvl[t]] + [words(p) for p in level])
+            nxt = []
+            for q in range(0, len(level), 2):
+                L = level[q]
+                V = L ^ level[q + 1] if q + 1 < len(level) else L
+                if s[t] and V:
+                    rows.append((j, t, words(s[t]), words(V), words(L)))
+                    nxt.append(L ^ model.clmul_fast(s[t], V))
+                else:
+                    nxt.append(L)
+            level = nxt
+        lvl[k] = max(lvl[k], words(level[0]))
+    return rows, lvl
+
+
+def write_trace(arr, s, x):
+    """array_write_kernel on one array: the indicator Q_0 of every element by suffix products,
+    then per bit wave_mul(X, nx, Q0, nind, T, nt, O) with X = x_j + T_j the uniform operand.
+    Rows (v, j, nx, nind, nt)."""
+    k = am.index_bits(len(arr))
+    rows, qmax = [], 0
+    for v, el in enumerate(arr):
+        ind = am.indicator(s, v, k, model.clmul_fast)
+        qmax = max(qmax, words(ind))
+        for j, (T, xj) in enumerate(zip(el, x)):
+            if ind and xj ^ T:
+                rows.append((v, j, words(xj ^ T), words(ind), words(T)))
+    return rows, qmax
+
+
+def check_array_path(name):
+    """The paths of the array cases and plan_array_read's / plan_array_write's buffers from the plan
+    driver, filled."""
+    c = inputs("array", name)
+    count, k = c["count"], c["k"]
+    ba, bx, bs = ([int(b) for b in c[key]] for key in ("ba", "bc", "bb"))
+    S = sum(bs[:k])
+    rt = [read_trace(arr, s) for arr, s in zip(c["arrays"], c["B"])]
+    wt = [write_trace(arr, s, x) for arr, s, x in zip(c["arrays"], c["B"], c["C"])]
+    l1 = max((r for t in rt for r in t[0] if r[1] == 1), key=lambda r: r[2] + r[3])
+    wr = max((r for t in wt for r in t[0]), key=lambda r: r[2] + r[3])
+    if name == "w1_edge":
+        assert l1[2:4] == (8, 56) and wr[2:4] == (48, 16)
+    elif name == "w2_edge":
+        assert l1[2:4] == (8, 57) and wr[2:4] == (49, 16)
+    elif name == "count5_per_bit":
+        assert (count, k) == (5, 3) and len(set(ba)) == 8
+        # the last element rises alone: V = Add = the node at levels 0 and 1
+        assert any(r[3] == r[4] and r[1] < 2 for t in rt for r in t[0])
+    else:
+        raise KeyError(name)
+    ob, vals, _, _ = array_reference(name, "read")
+    _reaches(vals, ob)
+    p = array_plan("read", count, ba, bs)
+    assert p["status"] == 0 and p["lds_per_wave"] <= SHARE_WORDS and p["bounds"] == ob.tolist()
+    lv = [max(t[1][q] for t in rt) for q in range(k + 1)]
+    bound = [max(ba) + sum(bs[:q]) for q in range(k + 1)]
+    assert lv == [wob(b) for b in bound]  # every level's widest node, the root's included
+    ends = [p["oL"], p["oX"], p["oP"], p["oP"] + p["cP"], p["oP"] + 2 * p["cP"]] + \
+        p["slot"][1:k] + [p["lds_per_wave"]]
+    sizes = [b - a for a, b in zip(ends, ends[1:])]
+    for size, q in zip(sizes, [0, k - 1, k, k] + list(range(k))):
+        assert lv[q] <= size <= lv[q] + 2, (sizes, lv)
+    assert p["slot"][0] == p["oP"] + 2 * p["cP"]
+    ob, vals, _, _ = array_reference(name, "write")
+    _reaches(vals, ob)
+    p = array_plan("write", count, ba, bs, bx)
+    assert p["status"] == 0 and p["lds_per_wave"] <= SHARE_WORDS and p["bounds"] == ob.tolist()
+    wide = max(max(ba), max(bx))
+    assert max(t[1] for t in wt) == wob(S) and wr[2] == wob(wide)
+    osize = p["qoff"][k - 1] - p["oO"]
+    assert wr[2] + wr[3] == wob(S) + wob(wide) <= osize <= wob(S + wide) + 2
+    assert p["oO"] - p["oX"] >= wr[2] and p["oO"] - p["oX"] - wr[2] <= 2
+    return dict(read=l1, write=wr)
+
+
+_WAVE_FAMILIES = {"select": _select_inputs, "minmax": _minmax_inputs, "lookup": _lookup_inputs,
+                  "shift": _shift_inputs, "count": _count_inputs, "array": _array_inputs}

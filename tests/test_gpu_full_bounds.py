@@ -1,5 +1,6 @@
 """GPU: every circuit kernel on operands that FILL their static bounds (tests/synth.py), bit-exact
-against the model circuits that test_synth_reference.py pins to the C oracle on the CPU.
+against the model circuits that test_synth_reference.py pins on the CPU (to the C oracle, or for
+select, min / max, lookup, shift, the bit counts and the array circuits to a second evaluation).
 
 The other parity tests feed the engine genuine fresh encryptions, whose bits have degree at most
 d + d' whatever bound their batch was allocated with; here the polynomials are synthetic (uploaded
@@ -351,3 +352,201 @@ def test_decrypt(H, world, oracle, name):
     la, da, _, _ = synth.packed("dec", name)
     assert np.array_equal(got, oracle.decrypt_batch(sk, la, da, c["ba"], 8, c["n"]).reshape(-1))
     assert np.array_equal(got, synth.dec_reference(name).reshape(-1))
+
+
+# ------------------------------------------------------------------ select, min / max
+def _from_host(H, ctx, limbs, deg, bound, n):
+    return H.Ciphered.from_host(limbs, deg, bound, n, ctx.device, None)
+
+
+@pytest.mark.parametrize("name", list(synth.SELECT_CASES))
+def test_select(H, world, name):
+    """select_kernel (kernels.hip): wave_mul<kQSmall = 10, 8>(X, nx, C, nc, Bb, nb, T) per bit, x_i
+    = a_i + b_i the uniform operand, the condition c the per-lane one, b_i added: nout = max(nx +
+    nc, nb) words, W = ceil(nout / 64) up to 8, MULTI tiles past 512, x_i read in chunks of 10
+    words.  u8; 8 scheduled values whose condition cycles through the kinds (NULL: a null product,
+    an exact copy of b_i; UNIT: nc = 1), then a FULL against b one below its bound and the other
+    way round under a FULL condition.  Paths (synth.check_select_path; condition / a, b bounds):
+      w1_edge        1023 / 1023   nx + nc = 32 + 32 = 64, the last W = 1 product
+      w2_edge        1023 / 1055   33 + 32 = 65, the first W = 2
+      one_tile       8191 / 8191   256 + 256 = 512: exactly one W = 8 tile
+      multi_tile     8191 / 8223   257 + 256 = 513: a MULTI tile of one word
+      chunks_10_11   500 / 319, 320   nx = 10 and 11: one and two uniform chunks
+      chunks_20_21   500 / 639, 640   nx = 20 and 21: two and three
+      lopsided       9000 / 40     nx = 2 against nc = 282; swapped (40 / 9000): nx = 282, 29
+                                   chunks, against nc = 2
+      per_bit        500 / a: 64 i + 63, b: 1000 - 97 i   capacities distinct within each operand,
+                     every slot filled; two more values with x_i of one word under a one-word
+                     condition: nb > nx + nc, nout = nb, at every bit but bit 0
+    Every slot of plan_select (SC, SA, SB, SX and T = SC + SX + 2) is filled to the last word its
+    bound allows and every output bit reaches hm_select_out_bounds."""
+    ctx = world()
+    c = synth.inputs("select", name)
+    la, da, lb, db, lc, dc = synth.packed("select", name)
+    a = _from_host(H, ctx, la, da, c["ba"], c["n"])
+    b = _from_host(H, ctx, lb, db, c["bb"], c["n"])
+    cond = _from_host(H, ctx, lc, dc, c["bc"], c["n"])
+    out = ctx.select(cond, a, b)
+    ctx.synchronize()
+    ob, _, rl, rd = synth.select_reference(name)
+    same(out, ob, rl, rd, c["n"], f"select {name}")
+
+
+@pytest.mark.parametrize("signed", [False, True])
+@pytest.mark.parametrize("name", list(synth.MINMAX_CASES))
+def test_min_max(H, world, name, signed):
+    """minmax_kernel (kernels.hip): phase 1 is borrow_step through the top bit (the paths of
+    test_sub_and_comparisons, on the operands of every synth.BORROW_CASES entry); phase 2 is
+    wave_mul<kQSmall, 8>(X, nx, W, nw, is_max ? Ab : Bb, ..., Wn) with W = w_n kept in a borrow
+    buffer of cw = SX + chain / 32 + 3 words (plan_borrow with chain = wb_L).  Paths
+    (synth.check_minmax_path):
+      u8_b700, u16_per_bit, u8_pair_b255   the borrow cases' operands (u16_per_bit with one all-FULL
+                     value more: x_15 w_16 spans more than 512 words, a MULTI tile)
+      p2_one_tile    uniform 1632: nw = 460, nx = 52, nx + nw = 512 = one W = 8 tile
+      p2_multi_tile  uniform 1636: nw = 461, nx + nw = 513
+      null_borrow    uniform 255: a = b bit for bit over {0, 1} and b null under a of every kind
+                     leave w_n null: phase 2's product is null over nout = max(nx, nadd) words and
+                     the operand is copied through Add (min: b, max: a)
+    The borrow buffer is filled to the last word the bounds allow; every output bit reaches
+    hm_minmax_out_bounds (bit 0 under ba_0 = bb_0: one below, the most any data can).  Min and
+    max, unsigned and signed, against select_model."""
+    ctx = world()
+    c, a, b = upload(H, ctx, "minmax", name)
+    for op, cls in (("min", H.HomomorphicMin), ("max", H.HomomorphicMax)):
+        out = ctx.apply2(cls, a, b, signed=signed)
+        ob, _, rl, rd = synth.minmax_reference(name, op, signed)
+        same(out, ob, rl, rd, c["n"], f"{op} {name} signed={signed}")
+    ctx.synchronize()
+
+
+# ------------------------------------------------------------------ lookup
+@pytest.mark.parametrize("which", synth.LOOKUP_TABLES)
+@pytest.mark.parametrize("name", list(synth.LOOKUP_CASES))
+def test_lookup(H, world, name, which):
+    """lookup_kernel (kernels.hip) in plan_lookup's layout (lookup_host.h: one slot per monomial at
+    off[], the inner sum I of cI words, two accumulators of cP = even(cI + cH) + 2): the monomials
+    by doubling, wave_mul<kQSmall, 8>(a_i, nb, M[s], ..) with a_i uniform, then per output bit
+    lookup_inner_sum's cI loop and the accumulate wave_mul(MH[t], nh, I, ni, P, np, Pn).  Tables:
+    all = t[0] = 1 (every ANF coefficient set), top = t[2^k - 1] = 1 (the top monomial alone),
+    random = seeded.  8 scheduled values (a NULL index bit nulls every monomial above it: `if
+    (!nh) continue` and the N[id] = 0 flows; a UNIT bit makes the product a copy) + 2 all-FULL.
+    Paths (synth.check_lookup_path; k, index bounds):
+      w1_edge        2; 1023, 1023   accumulate nh + ni = 32 + 32 = 64
+      w2_edge        2; 1023, 1055   33 + 32 = 65
+      one_tile       8; 2040 x 8     256 + 256 = 512: one W = 8 tile; every doubling slot, cI, cH
+                                     and cP filled (5416 of 10 240 LDS words)
+      multi_tile     8; a_7 = 2072   257 + 256 = 513: a MULTI tile
+      chunks_319 .. chunks_640   4; uniform   the doubling's uniform a_i at 10, 11, 20, 21 words
+      odd_split_per_bit  5 (kl = 3, kh = 2); 63 + 97 i, the low 5 bits of a u16 batch: distinct
+                     slot sizes per monomial; the `need` mask under the random table
+      wide_out       3; 700; a u32 table   32 output bits, P / Pn exchanged in every one (all and
+                     top set all 32 bits of their one entry)
+    Bit-exact against lookup_model."""
+    ctx = world()
+    c, a, _ = upload(H, ctx, "lookup", name)
+    out = ctx.lookup(a, synth.lookup_table(name, which), in_bits=c["k"])
+    ctx.synchronize()
+    ob, _, rl, rd = synth.lookup_reference(name, which)
+    same(out, ob, rl, rd, c["n"], f"lookup {name} {which}")
+
+
+# ------------------------------------------------------------------ shift
+@pytest.mark.parametrize("mode", synth.shm.MODES, ids=lambda m: m[0] + ("_signed" if m[1] else ""))
+@pytest.mark.parametrize("name", list(synth.SHIFT_CASES))
+def test_shift(H, world, name, mode):
+    """shift_kernel (kernels.hip) in plan_shift's layout (shift_host.h: in-place slots off[i] of
+    even(need[i] / 32 + 2) words, the X / T buffers at the widest slot, the rotates' save area
+    sv[t] at "amount bounds above t + widest a"): stages from t = L - 1 down to `last`, per product
+    wave_mul<kQSmall, 8>(S, ns, V, nv, xi, ni, T) with s_t uniform and V = x_i + x_src; the last
+    stage stores from T.  The amount's bits cycle through the kinds (a NULL s_t is a skipped stage).
+    Paths (synth.check_shift_path; amount bounds / value bounds; all five modes):
+      w1_edge        255 x 3 / 1279   final product ns + nv = 8 + 56 = 64
+      w2_edge        255 x 3 / 1311   8 + 57 = 65
+      one_tile       255 x 3 / 15615  8 + 504 = 512; the rotates' sv[2] area (4 x 490) filled;
+                                      7144 of 10 240 LDS words
+      multi_tile     255 x 3 / 15647  8 + 505 = 513
+      chunks         319, 320, 639 / 200 + 7 i   s_t at 10, 11 and 20 words in the three stages
+      per_bit        63, 700, 320 / 63 .. 511 .. 127   per-bit need[i] slots (prefix maxima for
+                     SHL, suffix maxima for SHR), each filled as far as the stages above the last
+                     can fill it
+      stage_subsets  255 x 3 / 300 + 5 i   value e has s_t NULL iff bit t of e is clear: last = -1
+                     (the copy-out), 0, 1, 2 and a skipped middle stage, FULL values
+      u32_headline_shape  256 x 5 / 256 x 32, parameters (128, 128, 1, 128): five stages, 32 slots
+                     at 1536
+    Uniform value bounds end on values with one FULL bit and the others one below (equal tops
+    cancel by parity).  Bit-exact against shift_model."""
+    op, signed = mode
+    c = synth.inputs("shift", name)
+    ctx = world(c["params"])
+    _, a, s = upload(H, ctx, "shift", name)
+    cls = {"shl": H.HomomorphicShiftLeft, "shr": H.HomomorphicShiftRight,
+           "rotl": H.HomomorphicRotateLeft, "rotr": H.HomomorphicRotateRight}[op]
+    out = ctx.shift(cls, a, s, signed=signed)
+    ctx.synchronize()
+    ob, _, rl, rd = synth.shift_reference(name, op, signed)
+    same(out, ob, rl, rd, c["n"], f"{op} {name} signed={signed}")
+
+
+# ------------------------------------------------------------------ counts, runs, array
+@pytest.mark.parametrize("name", list(synth.COUNT_CASES))
+def test_bit_counts(H, world, name):
+    """bitcount_kernel and bitrun_kernel (kernels.hip) in plan_bitcount's layout (bitcount_host.h:
+    the slots E_1 .. E_J or the runs' accumulators at off[], T, the running product's D / Dn of cD
+    words; a wave's slice within 2560 words): every product wave_mul<kQSmall, 8>(U, nu, P, np, ..)
+    with the literal uniform.  u8, 8 scheduled values, then all FULL and seven FULL with bit 3 one
+    below (equal tops cancel by parity in a symmetric sum).  Paths (synth.check_count_path), all six
+    ops unless noted:
+      w1_edge        255 x 8       the last running product u_8 (u_1 .. u_7): 8 + 56 = 64 words
+      w2_edge_top    bit 7 at 287  9 + 56 = 65 for the counts and the trailing runs (8 + 57 for the
+                                   leading runs, whose last literal is bit 0)
+      w2_edge_low    bit 0 at 287  9 + 56 = 65 for the leading runs (8 + 57 for the others)
+      chunks_319, chunks_320       the literal at 10 and 11 words: one and two uniform chunks
+      one_tile       2047 x 8      counts only (the planner refuses the runs there): 64 + 448 = 512
+                                   = one W = 8 tile; 2006 of 2560 LDS words
+      multi_tile     bit 7 at 2079 counts only: 65 + 448 = 513, a MULTI tile
+    Every output's slot or accumulator and D / Dn are filled to the last word their bounds allow.
+    Bit-exact against bitcount_model."""
+    import bitcount_model as bcm
+    ctx = world()
+    c, a, _ = upload(H, ctx, "count", name)
+    for op in synth.COUNT_CASES[name][1]:
+        cls = getattr(H, "Homomorphic" + "".join(w.title() for w in op.split("_")))
+        out = ctx.bit_count(cls, a)
+        ob, _, rl, rd = synth.count_reference(name, op)
+        same(out, ob, rl, rd, c["n"], f"{op} {name}")
+    assert set(synth.COUNT_CASES[name][1]) <= set(bcm.OPS)
+    ctx.synchronize()
+
+
+@pytest.mark.parametrize("what", ["read", "write"])
+@pytest.mark.parametrize("name", list(synth.ARRAY_CASES))
+def test_array(H, world, name, what):
+    """array_read_kernel and array_write_kernel (kernels.hip) in plan_array_read's / plan_array_write's
+    layouts (array_host.h; a wave's slice within 2560 words).  Read: a level-t join is
+    wave_mul<kQSmall, 8>(s_t, ns, V, nv, Add, nadd, ..) with V = L + R; write: wave_mul(X, nx, Q0,
+    nind, T, nt, O) with X = x_j + T_j uniform and Q0 the element's indicator.  8 scheduled arrays
+    (element v's kinds shifted by v, the index bits and the written value on schedules of their
+    own), then one FULL element among elements one below their bound, then all FULL under an x one
+    below.  Paths (synth.check_array_path):
+      w1_edge        count 4, index 255 x 2, elements and x at 1535: the read's level-1 product
+                     8 + 56 = 64 words, the write's ind (x + T) 16 + 48 = 64
+      w2_edge        ... at 1567: 8 + 57 = 65 and 16 + 49 = 65
+      count5_per_bit count 5 (k = 3, no power of two: the last element rises alone), elements
+                     63 + 97 i, x 700 - 83 i
+    Every level's node buffer, the root's included, and the write's X and O are filled.  Bit-exact
+    against array_model."""
+    ctx = world()
+    c = synth.inputs("array", name)
+    la, da, ls, ds, lx, dx = synth.packed("array", name)
+    arr = _from_host(H, ctx, la, da, c["ba"], c["n"] * c["count"])
+    idx = _from_host(H, ctx, ls, ds, c["bb"], c["n"])
+    if what == "read":
+        out = ctx.array_read(arr, idx, c["count"])
+        nout = c["n"]
+    else:
+        x = _from_host(H, ctx, lx, dx, c["bc"], c["n"])
+        out = ctx.array_write(arr, idx, x, c["count"])
+        nout = c["n"] * c["count"]
+    ctx.synchronize()
+    ob, _, rl, rd = synth.array_reference(name, what)
+    same(out, ob, rl, rd, nout, f"array {what} {name}")

@@ -5,6 +5,10 @@ synthetic operands (borrow_model has no second implementation: its ring identiti
 are checked instead), every output degree is within the engine's static output bounds
 (H.*_out_bounds, which the Python restatements of synth.py must equal), and the case's path
 assertion holds on the model's integers, so a case that stops reaching its path fails here.
+
+The families of select, min / max, lookup, shift, the bit counts and the array circuits have no C
+restatement: each model is pinned by a second evaluation order (or in the residue ring) instead,
+and their plans come from the stand-alone plan drivers of tests/sanitize/.
 """
 import numpy as np
 import pytest
@@ -205,3 +209,185 @@ def test_dec_reference(oracle, name):
     assert np.array_equal(synth.dec_reference(name), want)
     assert 0 < int(np.unpackbits(want).sum()) < want.size * 8  # neither all zeros nor all ones
     synth.check_dec_path(name)
+
+
+# ------------------------------------------------------------------ select, min / max
+@pytest.mark.parametrize("name", list(synth.SELECT_CASES))
+def test_select_reference(H, name):
+    """select_model pinned by a second evaluation, b_i + c a_i + c b_i over the gate model (two
+    products on gf2_model.clmul_fast instead of one on clmul); bounds against hm_select_out_bounds;
+    the path, the fills and the plan's slots in synth.check_select_path."""
+    c = synth.inputs("select", name)
+    assert 8 <= c["n"] <= 12 and len(synth.packed("select", name)) == 6
+    ob, vals, _, _ = synth.select_reference(name)
+    assert np.array_equal(ob, H.select_out_bounds(c["bc"][0], c["ba"], c["bb"]))
+    within(vals, ob)
+    for cv, a, b, out in zip(c["C"], c["A"], c["B"], vals):
+        cc = [cv[0]] * len(a)
+        ca, cb = synth.gate_circuit("and", cc, a), synth.gate_circuit("and", cc, b)
+        assert [y ^ p ^ q for y, p, q in zip(b, ca, cb)] == out
+        assert cv[1:] == [0] * 7
+    synth.check_select_path(name)
+
+
+@pytest.mark.parametrize("name", list(synth.MINMAX_CASES))
+def test_minmax_reference(H, name):
+    """select_model's min / max pinned in the residue ring (a ring homomorphism): the borrow
+    recurrence run on the operands' residues, then b_i + w a_i + w b_i (min) or a_i + ... (max);
+    bounds against hm_minmax_out_bounds; synth.check_minmax_path."""
+    c = synth.inputs("minmax", name)
+    assert 8 <= c["n"] <= 12
+    g = residue_modulus(19)
+    mul = synth.model.residue_mul(g)
+    res = lambda p: synth.model.residue_int(p, g)  # noqa: E731
+    RA = [[res(p) for p in v] for v in c["A"]]
+    RB = [[res(p) for p in v] for v in c["B"]]
+    n = c["nbits"]
+    for signed in (False, True):
+        RW = []
+        for ra, rb in zip(RA, RB):
+            w = 0
+            for i in range(n):
+                gen = ra[i] if signed and i == n - 1 else rb[i]
+                w = mul(ra[i], rb[i]) ^ gen ^ mul(ra[i] ^ rb[i] ^ 1, w)
+            RW.append(w)
+        for op in ("min", "max"):
+            ob, vals, _, _ = synth.minmax_reference(name, op, signed)
+            assert np.array_equal(ob, H.minmax_out_bounds(c["ba"], c["bb"]))
+            within(vals, ob)
+            for ra, rb, w, out in zip(RA, RB, RW, vals):
+                keep = rb if op == "min" else ra
+                for i in range(n):
+                    assert res(out[i]) == keep[i] ^ mul(w, ra[i]) ^ mul(w, rb[i]), (op, signed, i)
+    synth.check_minmax_path(name)
+
+
+# ------------------------------------------------------------------ lookup
+@pytest.mark.parametrize("name", list(synth.LOOKUP_CASES))
+def test_lookup_reference(H, name):
+    """lookup_model pinned by the other doubling order: the reference multiplies the monomials up
+    from their lowest bit over all k index bits (lookup_model.monomials); synth.lookup_trace forms
+    them on the top bit within the low and the high half, as the kernel does, and accumulates
+    MH[t] I_jt on clmul_fast.  Both must give the same polynomials for all three tables; bounds
+    against hm_lookup_out_bounds and the plan driver; synth.check_lookup_path."""
+    import lookup_model as lm
+    c = synth.inputs("lookup", name)
+    assert 8 <= c["n"] <= 12
+    for which in synth.LOOKUP_TABLES:
+        t = synth.lookup_table(name, which)
+        ob, vals, _, _ = synth.lookup_reference(name, which)
+        assert np.array_equal(ob, H.lookup_out_bounds(c["ba"], t, c["k"]))
+        plan, tr = synth.lookup_traces(name, which)
+        assert plan["bounds"] == ob.tolist()
+        within(vals, ob)
+        assert [out for _, _, _, out in tr] == vals, which
+    t = synth.lookup_table(name, "random")
+    assert lm.lookup_circuit(c["A"][-1], t) == synth.lookup_reference(name, "random")[1][-1]
+    masks = lm.coefficient_masks(synth.lookup_table(name, "all"))
+    assert masks[0] == (1 << (1 << c["k"])) - 1  # t[0] = 1: every monomial in output bit 0
+    assert lm.coefficient_masks(synth.lookup_table(name, "top"))[0] == 1 << ((1 << c["k"]) - 1)
+    synth.check_lookup_path(name)
+
+
+# ------------------------------------------------------------------ shift
+@pytest.mark.parametrize("name", list(synth.SHIFT_CASES))
+def test_shift_reference(H, name):
+    """shift_model (stages ascending) pinned by the kernel's own order: synth.shift_trace runs the
+    stages from the widest step down on clmul_fast, skipping null amounts, and shift_circuit(order
+    descending) on the last value; bounds against hm_shift_out_bounds and the plan driver;
+    synth.check_shift_path in all five modes."""
+    import shift_model as shm
+    c = synth.inputs("shift", name)
+    assert 8 <= c["n"] <= 12
+    ops = {"shl": H.HomomorphicShiftLeft, "shr": H.HomomorphicShiftRight,
+           "rotl": H.HomomorphicRotateLeft, "rotr": H.HomomorphicRotateRight}
+    for op, signed in shm.MODES:
+        ob, vals, _, _ = synth.shift_reference(name, op, signed)
+        assert np.array_equal(ob, H.shift_out_bounds(ops[op], c["ba"], c["bb"]))
+        within(vals, ob)
+        assert [t[4] for t in synth.shift_traces(name, op, signed)] == vals, (op, signed)
+        down = shm.shift_circuit(op, c["A"][-1], c["B"][-1], signed, order=range(c["L"] - 1, -1, -1))
+        assert down == vals[-1]
+        synth.check_shift_path(name, op, signed)
+
+
+# ------------------------------------------------------------------ counts, runs, array
+def _esym(us, top, mul):
+    """e_0 .. e_top of the literals by halving: e_j(L + R) = sum_l e_l(L) e_{j-l}(R) -- not the
+    model's one-literal-at-a-time recurrence."""
+    if len(us) == 1:
+        return [1, us[0]] + [0] * (top - 1)
+    h = len(us) // 2
+    lo, hi = _esym(us[:h], top, mul), _esym(us[h:], top, mul)
+    out = [0] * (top + 1)
+    for a, x in enumerate(lo):
+        for b, y in enumerate(hi[:top + 1 - a]):
+            if x and y:
+                out[a + b] ^= mul(x, y)
+    return out
+
+
+@pytest.mark.parametrize("name", list(synth.COUNT_CASES))
+def test_count_reference(H, name):
+    """bitcount_model pinned in the residue ring by another evaluation order: the elementary
+    symmetric polynomials by halving (counts), the runs' prefixes multiplied from the far end;
+    bounds against hm_bitcount_out_bounds and the plan driver; synth.check_count_path per op."""
+    import bitcount_model as bcm
+    c = synth.inputs("count", name)
+    assert 8 <= c["n"] <= 12
+    g = residue_modulus(23)
+    mul = synth.model.residue_mul(g)
+    res = lambda p: synth.model.residue_int(p, g)  # noqa: E731
+    RA = [[res(p) for p in v] for v in c["A"]]
+    ops = {op: getattr(H, "Homomorphic" + "".join(w.title() for w in op.split("_")))
+           for op in bcm.OPS}
+    for op in synth.COUNT_CASES[name][1]:
+        run, zeros, leading = bcm.OPS[op]
+        ob, vals, _, _ = synth.count_reference(name, op)
+        assert np.array_equal(ob, H.bitcount_out_bounds(ops[op], c["ba"]))
+        within(vals, ob)
+        for ra, out in zip(RA, vals):
+            u = [x ^ 1 for x in ra] if zeros else list(ra)
+            if run:
+                v = u[::-1] if leading else u
+                want = [0] * 8
+                for j in range(1, 9):
+                    t = 1
+                    for x in reversed(v[:j]):
+                        t = mul(x, t)
+                    for k in range(4):
+                        if j % (1 << k) == 0:
+                            want[k] ^= t
+            else:
+                e = _esym(u, 8, mul)
+                want = [e[1 << k] if k < 4 else 0 for k in range(8)]
+            assert [res(p) for p in out] == want, op
+        assert [t[-1] for t in synth.count_traces(name, op)] == vals, op  # the pruned recurrence
+        synth.check_count_path(name, op)
+
+
+@pytest.mark.parametrize("name", list(synth.ARRAY_CASES))
+def test_array_reference(H, name):
+    """array_model's tree pinned by array_model.circuit_read_sum (the indicator sum), the write by
+    T + ind x + ind T on clmul_fast; bounds against hm_array_*_out_bounds and the plan driver;
+    synth.check_array_path."""
+    import array_model as am
+    c = synth.inputs("array", name)
+    assert 8 <= c["n"] <= 12 and len(c["A"]) == c["n"] * c["count"]
+    assert len(synth.packed("array", name)) == 6
+    fast = synth.model.clmul_fast
+    ob, vals, _, _ = synth.array_reference(name, "read")
+    assert np.array_equal(ob, H.array_read_out_bounds(c["ba"], c["count"], c["bb"]))
+    within(vals, ob)
+    for arr, s, out in zip(c["arrays"], c["B"], vals):
+        assert am.circuit_read_sum(arr, s, fast) == out
+    ob, vals, _, _ = synth.array_reference(name, "write")
+    assert np.array_equal(ob, H.array_write_out_bounds(c["ba"], c["bc"], c["count"], c["bb"]))
+    within(vals, ob)
+    at = 0
+    for arr, s, x in zip(c["arrays"], c["B"], c["C"]):
+        for v, el in enumerate(arr):
+            ind = am.indicator(s, v, c["k"], fast)
+            assert [T ^ fast(ind, xj) ^ fast(ind, T) for T, xj in zip(el, x)] == vals[at]
+            at += 1
+    synth.check_array_path(name)
