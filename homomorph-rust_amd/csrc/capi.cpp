@@ -6,8 +6,8 @@
 // and the plans come from host-only headers: the adder's from add_host.h (plan_add), the
 // wave-per-value circuits' from circuit_host.h (plan_gate, plan_borrow, plan_select),
 // lookup_host.h (plan_lookup), shift_host.h (plan_shift), bitcount_host.h (plan_bitcount) and
-// array_host.h (plan_array_read, plan_array_write); the
-// multiplier's from mul_host.cpp.
+// array_host.h (plan_array_read, plan_array_write); the multiplier's from mul_plan.h
+// (mul_result_bounds, mul_cost_model; its plans are built, cached and run by mul_host.cpp).
 // Never throws across the ABI.
 #include <hip/hip_runtime.h>
 
@@ -27,6 +27,7 @@
 #include "circuit_host.h"
 #include "ctx.h"
 #include "lookup_host.h"
+#include "mul_plan.h"
 #include "shift_host.h"
 
 using namespace hm;

@@ -8,13 +8,7 @@
 
 #include "engine.h"
 #include "gf2_wave.h"
-
-namespace hm {
-struct MulPlan; // mul_host.cpp
-// default Karatsuba scratch limit, words per value and lane (hm_ctx_set_mul_scratch): above it a
-// product is planned one subtree at a time (mul_host.cpp); every K <= 20 plan stays below it
-constexpr uint64_t kKaScratchWords = 200000000u;
-}
+#include "mul_plan.h"
 
 struct hm_ctx {
     uint16_t d, dp, delta, tau;
@@ -72,13 +66,13 @@ struct hm_ctx {
     };
     std::vector<Retired> retired;
     uint64_t generation = 0;
-    // column multiplier plans (device task tables), keyed by the operand bounds; see mul_host.cpp
+    // column multiplier plans (device task tables), keyed by the operand bounds (mul_host.cpp)
     std::vector<hm::MulPlan *> mul_plans; // owned; freed by mul_plans_release
     // Karatsuba carry products (hm_ctx_set_mul_options): shorter operand >= ka_min words (0 =
     // never), recursion down to leaves of at most ka_leaf words
     uint32_t ka_min = 256, ka_leaf = 256;
     // Karatsuba scratch per value and lane above which a product is planned one subtree at a
-    // time (hm_ctx_set_mul_scratch; mul_host.cpp kKaScratchWords)
+    // time (hm_ctx_set_mul_scratch; mul_plan.h kKaScratchWords)
     uint64_t ka_scratch = hm::kKaScratchWords;
     // where the Karatsuba leaf products run (hm_ctx_set_mul_products): HM_MUL_PRODUCTS_*
     uint32_t mul_products = 0;
@@ -202,12 +196,6 @@ void mul_plans_release(hm_ctx *c);
 // their leaves), for the low K output bits of the nbits-bit circuit (hm_mul_plan_work).
 hm_status mul_plan_work(hm_ctx *c, uint32_t nbits, uint32_t K, const uint32_t *a, const uint32_t *b,
                         bool is_signed, double &executed);
-// Degree bounds of the K low output bits of the nbits-bit circuit (-1 = always null); false when a
-// bound exceeds the engine's 2^30 limit.  The same symbolic walk as the plan.
-bool mul_result_bounds(uint32_t nbits, uint32_t K, const uint32_t *a, const uint32_t *b,
-                       bool is_signed, std::vector<int64_t> &res);
-// The same walk over bounds only, without limits: word-pair products, output bytes, max degree.
-void mul_cost_model(uint32_t nbits, uint32_t K, const uint32_t *a, const uint32_t *b,
-                    double &pairs, double &out_bytes, double &maxdeg);
+// (mul_result_bounds and mul_cost_model, which need no context: mul_plan.h)
 
 } // namespace hm

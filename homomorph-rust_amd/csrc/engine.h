@@ -1,6 +1,6 @@
 // engine.h — argument blocks shared by the HIP kernels (kernels.hip) and the C-ABI host code
 // (capi.cpp; the adder's plan fields are filled by add_host.h, the multiplier's by
-// mul_host.cpp).  Plain structs passed to kernels by value.
+// mul_plan.h and mul_host.cpp).  Plain structs passed to kernels by value.
 #pragma once
 #include <stdint.h>
 
@@ -321,7 +321,7 @@ static_assert(sizeof(ShiftArgs) < 4096 && sizeof(LookupArgs) < 4096 && sizeof(Se
                   sizeof(ArrayWriteArgs) < 4096,
               "kernarg limit");
 
-// Column-parallel carry-save multiplier (mul_engine.hip, mul_host.cpp).  Column i of
+// Column-parallel carry-save multiplier (mul_engine.hip, mul_plan.h).  Column i of
 // mul_unsigned_internal (common.rs:66-105) XORs its items x_0..x_{n-1} (the partial products
 // a_j b_{i-j}, then the previous column's carries) into result_i and pushes the carry
 // (x_0 ^ .. ^ x_{t-1}) * x_t before each XOR.  With the prefixes p_t = x_0 ^ .. ^ x_{t-1}
@@ -373,7 +373,7 @@ struct MulProdTask {
 struct MulTile {
     uint32_t task, base; // output words [base, base + 64 W) of task
 };
-// One span of an MFMA schoolbook product, resolved on the host (mul_host.cpp build_plan): the
+// One span of an MFMA schoolbook product, resolved on the host (mul_plan.h build_plan): the
 // operands' and the output's arena offsets and slots, so a wave's only dependent loads after this
 // one record are the operands' degrees (instead of span -> task -> slots -> degrees).
 struct MulSpanRec {
@@ -387,7 +387,7 @@ struct MulProdArgs {
     const MulTile *tiles;
     uint32_t ntiles;
 };
-// Karatsuba products (mul_host.cpp "Karatsuba"): the big carries p_t * x_t of the deep columns
+// Karatsuba products (mul_plan.h "Karatsuba"): the big carries p_t * x_t of the deep columns
 // run as a recursion over arena VIEWS (u32-word ranges of a value's arena; words past `valid`
 // read as zero).  Level by level: sums of halves (KaSum), leaf products (MulVTask, schoolbook
 // tiles), and recombination R = z0 + (z0 + z1 + z2) X^h + z1 X^2h (KaComb).
@@ -478,11 +478,31 @@ struct MulMfmaArgs {
     uint32_t lean;        // leaves: the lean instance (per-group U windows, 4 waves per SIMD)
     uint32_t per_wave;    // work items per wave (set by launch_mul_mfma)
 };
+// A wave's LDS slice of the MFMA product kernels, in words: the kernels (mul_mfma.hip) lay their
+// slices out with these functions and the host (mul_plan.h) sizes the launches with them.
+constexpr int kMfG = 16;             // chunks per full A group (64 VGPRs of A fragments)
+constexpr int kVPad = 2 * kMfG + 32; // V words read beyond V's ends (zero)
+// U blocks of at most ub = min(umax, kMfUB) words: the launch's LDS slices are sized for them
+// (a launch of narrow schoolbook products reserves no 256-word U image, so more waves fit a CU)
+constexpr uint32_t mf_ub(uint32_t umax) { return umax < kMfUB ? umax : kMfUB; }
+constexpr uint32_t mf_rs_words(uint32_t umax) { return 4 * (mf_ub(umax) + 2) + 16; }
+// V words one (block, span) reaches: 32 span + 32 + 2 NC (NC <= ub/2 + 1), or all of V plus its
+// zero pads when that is fewer
+constexpr uint32_t mf_vi_words(uint32_t vmax, uint32_t span, uint32_t umax) {
+    const uint32_t a = 32 * span + 32 + 2 * (mf_ub(umax) / 2 + 1), b = vmax + 2 * kVPad;
+    return 4 * ((a < b ? a : b) + 8);
+}
+constexpr uint32_t mf_wave_words(uint32_t vmax, uint32_t span, uint32_t umax) {
+    return mf_rs_words(umax) + mf_vi_words(vmax, span, umax) + 32 * span;
+}
+// the U image of the windowed (lean) instances: one group of G chunks' window, RS quads
+// Qlo = 2 c0 + 1 .. Qlo + 2G + 1 (mul_mfma.hip mf_win_word)
+constexpr uint32_t mf_win_words(int G) { return 4u * (2u * (uint32_t)G + 2u) + 16u; }
 // Partial products grouped by their shared factor a_j (mul_mfma.hip mul_ppg_kernel): every
 // a_j * b_k of the plan in one launch before the columns, one wave per (value, a_j), a_j's A
 // fragments built once for all of its products (a_j within kMfPPGWords words: one chunk group of
 // at most kMfPPGWords / 2 + 1 = 17 chunks, as many as the kernel holds A fragments for; 34 words
-// would be 18).  Wider operands take the per-column launches (mul_host.cpp ppm).
+// would be 18).  Wider operands take the per-column launches (mul_plan.h ppm).
 constexpr uint32_t kMfPPGWords = 33;
 // b_k words staged per batch of partial products (mul_ppg_kernel: kMfPPGBatch x 64 LDS words)
 constexpr uint32_t kMfPPGBatch = 8;
@@ -620,8 +640,6 @@ int launch_mul_mfma(const MulMfmaArgs &a, bool leaf, void *stream);
 int launch_mul_ppg(const MulPPGArgs &a, void *stream);
 int launch_mul_ppv(const MulPPVArgs &a, void *stream);
 int launch_mul_rows(const MulRowArgs &a, void *stream);
-uint32_t mul_mfma_wave_words(uint32_t vmax, uint32_t span, uint32_t umax);
-uint32_t mul_mfma_lean_leaf_wave_words(uint32_t vmax, uint32_t span, uint32_t umax);
 int launch_ka_comb(const KaCombArgs &a, void *stream);
 int launch_mul_deg(const MulDegArgs &a, void *stream);
 constexpr uint32_t kMulTileW[] = {1, 2, 4, 8, 12}; // per-lane tile widths of the product launches

@@ -326,7 +326,7 @@ int launch_mul_pp(const MulPPArgs &P, void *stream) {
 //   - The column's slot records (item t, and the slot that receives p_{t+1} or the output bit)
 //     are copied into LDS once per block: read per item through items[] -> slots[], they were
 //     two dependent scalar loads each, twice per item, and the kernel waited ~90 % of its cycles.
-//   - Items live in the pp / carry regions and prefixes in their own region (mul_host.cpp
+//   - Items live in the pp / carry regions and prefixes in their own region (mul_plan.h
 //     build_plan), so no store aliases a later item: kScanBatch item loads are issued together,
 //     ahead of the XORs and stores.
 constexpr uint32_t kScanBatch = 8;
@@ -453,7 +453,7 @@ int launch_mul_prod(const MulProdArgs &P, uint32_t w, void *stream) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Karatsuba over arena views (mul_host.cpp "Karatsuba").  All offsets and h are multiples of 4
+// Karatsuba over arena views (mul_plan.h "Karatsuba").  All offsets and h are multiples of 4
 // words, so every access is a whole uint4; one wave per (value, task, 256-word chunk).
 
 // dst[0:h) = src[0:h) ^ src[h:2h), words at or past `valid` of src read as zero

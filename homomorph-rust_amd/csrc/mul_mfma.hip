@@ -4,7 +4,7 @@
 // Polynomial::mul (src/polynomial.rs:252-310): exact, so every bit is identical.
 //
 // Two kinds of task, one kernel body:
-//   LEAF  the Karatsuba leaves (mul_host.cpp "Karatsuba"): arena views with explicit sizes;
+//   LEAF  the Karatsuba leaves (mul_plan.h "Karatsuba"): arena views with explicit sizes;
 //   SLOT  the schoolbook carry products p_t * x_t of the column plan: slots whose exact sizes come
 //         from their degree rows (deg1), U = the operand with fewer words.
 // One wavefront per (value, task, output span of `span` tiles of 32 words).  U is taken in blocks
@@ -25,8 +25,6 @@
 
 namespace hm {
 
-constexpr int kMfG = 16;      // chunks per full A group (64 VGPRs of A fragments)
-
 // Phase timers (diagnostic builds with -DHM_MF_PROFILE only; the library never has them): per
 // launch class (the instance's template key), s_memtime deltas summed over waves for the record
 // loads, the operand images, the chunk groups (A fragments + tiles) and the copy-out, plus the
@@ -44,21 +42,7 @@ __device__ unsigned long long g_mf_prof[8][8];
 #define HM_MF_PF 3
 #endif
 constexpr int kMfPf = HM_MF_PF; // B reads issued ahead of their MFMA
-constexpr int kVPad = 2 * kMfG + 32; // V words read beyond V's ends (zero)
-
-// U blocks of at most ub = min(umax, kMfUB) words: the launch's LDS slices are sized for them
-// (a launch of narrow schoolbook products reserves no 256-word U image, so more waves fit a CU)
-__host__ __device__ constexpr uint32_t mf_ub(uint32_t umax) { return umax < kMfUB ? umax : kMfUB; }
-__host__ __device__ constexpr uint32_t mf_rs_words(uint32_t umax) { return 4 * (mf_ub(umax) + 2) + 16; }
-// V words one (block, span) reaches: 32 span + 32 + 2 NC (NC <= ub/2 + 1), or all of V plus its
-// zero pads when that is fewer
-__host__ __device__ constexpr uint32_t mf_vi_words(uint32_t vmax, uint32_t span, uint32_t umax) {
-    const uint32_t a = 32 * span + 32 + 2 * (mf_ub(umax) / 2 + 1), b = vmax + 2 * kVPad;
-    return 4 * ((a < b ? a : b) + 8);
-}
-__host__ __device__ constexpr uint32_t mf_wave_words(uint32_t vmax, uint32_t span, uint32_t umax) {
-    return mf_rs_words(umax) + mf_vi_words(vmax, span, umax) + 32 * span;
-}
+// (kMfG, kVPad and the LDS slice sizes mf_rs_words .. mf_win_words: engine.h)
 
 __device__ __forceinline__ int floor_div32(int x) { return x >= 0 ? x / 32 : -((31 - x) / 32); }
 
@@ -241,7 +225,7 @@ __device__ __forceinline__ void mf_v_image(const uint32_t *V, int nv, int vlo, i
 // One group of G chunks from c0 whose A fragments come from a window of the U image built for
 // this group alone (the lean leaf instance keeps no whole-U image): RS quads Qlo = 2 c0 + 1 ..
 // Qlo + 2G + 1, i.e. U words q = R - 1 - Q (zero outside [0, ub)), are all its fragments read
-__host__ __device__ constexpr uint32_t mf_win_words(int G) { return 4u * (2u * (uint32_t)G + 2u) + 16u; }
+// (mf_win_words(G) words, engine.h)
 // lane k's U word of the window of the group of G chunks from c0 (k < 2G + 2 <= 36 lanes)
 __device__ __forceinline__ uint32_t mf_win_word(const uint32_t *Ub, int ub, int R, int c0, int G,
                                                 const uint32_t *Ub2, int ub2) {
@@ -285,7 +269,7 @@ __device__ __forceinline__ void mf_group_win(uint32_t wword, const uint32_t *Ub,
 #endif
 // LEAN instances trade the paired tile chains for occupancy: one tile at a time, <= 128 VGPRs,
 // 4 waves per SIMD.
-//  - schoolbook (LEAF false): the launches whose U has at most kMfNarrowWords words (mul_host.cpp).
+//  - schoolbook (LEAF false): the launches whose U has at most kMfNarrowWords words (mul_plan.h).
 //    Such a wave is short (a 33-word U is 17 chunks: ~76 MFMAs) and waits on its record and operand
 //    loads for much of its life; the host sizes the narrow spans so 16 waves' LDS slices fit.
 //  - leaves (LEAF true): no whole-U image either, only each group's window (mf_group_win), so a
@@ -644,14 +628,6 @@ int launch_mul_mfma(const MulMfmaArgs &args, bool leaf, void *stream) {
         hipLaunchKernelGGL((mul_mfma_kernel<false, true, true>), grid, block, lds, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(mul_mfma_kernel<false>, grid, block, lds, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-uint32_t mul_mfma_wave_words(uint32_t vmax, uint32_t span, uint32_t umax) {
-    return mf_wave_words(vmax, span, umax);
-}
-
-uint32_t mul_mfma_lean_leaf_wave_words(uint32_t vmax, uint32_t span, uint32_t umax) {
-    return mf_win_words(kMfG + 1) + mf_vi_words(vmax, span, umax) + 32 * span;
 }
 
 } // namespace hm

@@ -3,7 +3,7 @@
 // engine library's host code throws std::bad_alloc, for every n up to the entry point's last
 // allocation, and checks that each host-only entry returns HM_ERR_OUT_OF_MEMORY (or HM_OK once no
 // allocation fails) instead of unwinding into the caller.  hm_mul_out_bounds runs the
-// multiplier's plan builder (mul_host.cpp build_plan) on the host, so a failure anywhere inside
+// multiplier's plan builder (mul_plan.h build_plan) on the host, so a failure anywhere inside
 // the plan is covered.  No hm_ctx is created, so no GPU is needed.  Built (unsanitised) and run
 // by tests/test_sanitize.py.
 #include <cstdio>

@@ -1,46 +1,37 @@
-// Host-only census of one multiplier plan (mul_host.cpp), under ASan/UBSan: the planner source is
-// compiled into this driver, no hm_ctx and no GPU.  Built by tests/sanitize/Makefile, run by
-// tests/synth.py mul_census (the full-bounds tier's path assertions read the planner's own output,
-// not a restatement of its rules).
+// Host-only census of one multiplier plan (mul_plan.h), under ASan/UBSan: the planner header is
+// compiled into this driver and nothing else is linked, no hm_ctx and no GPU.  Built by
+// tests/sanitize/Makefile, run by tests/synth.py mul_census (the full-bounds tier's path assertions
+// read the planner's own output, not a restatement of its rules).
 //
 //   plan_census L K signed ka_min ka_leaf mfma  a_0 .. a_{K-1}  b_0 .. b_{K-1}
 //
 // prints one JSON object: the plan-level choice of the partial products' launch, and per column
-// every launch mul_columns would make with the sizes the kernels are given.  "instance" is what
-// launch_mul_ppg / launch_mul_mfma (mul_mfma.hip) would pick for the launch: only their umax
-// comparisons are restated here, each beside the line it restates.
-#include "../../homomorph-rust_amd/csrc/mul_host.cpp"
+// every launch mul_columns would make with the sizes the kernels are given (runs_ppv, runs_ppg,
+// ka_leaf_launch: the functions mul_columns and run_ka call).  "instance" is what launch_mul_ppg /
+// launch_mul_mfma (mul_mfma.hip) would pick for the launch: only their umax comparisons are
+// restated here.
+#include "../../homomorph-rust_amd/csrc/mul_plan.h"
 
 #include <cstdio>
 #include <cstdlib>
 #include <string>
 
-// launch_mul_ppg (mul_mfma.hip:614-617): `a.umax <= kMfTinyWords` -> mul_ppg_kernel<kMfTinyChunks>,
-// else mul_ppg_kernel<kMfG + 1>; mul_columns (mul_host.cpp:904) takes mul_ppv_kernel first
+// launch_mul_ppg: `a.umax <= kMfTinyWords` -> mul_ppg_kernel<kMfTinyChunks>, else
+// mul_ppg_kernel<kMfG + 1>
 static const char *pp_instance(const hm::MulPlan &P) {
-    if (P.ppg && P.ppv && !P.ppv_tasks.empty()) return "mul_ppv_kernel";
-    if (P.ppg && !P.ppg_groups.empty())
-        return P.ppg_umax <= hm::kMfTinyWords ? "mul_ppg_kernel<11>" : "mul_ppg_kernel<17>";
+    if (hm::runs_ppv(P)) return "mul_ppv_kernel";
+    if (hm::runs_ppg(P)) return P.ppg_umax <= hm::kMfTinyWords ? "mul_ppg_kernel<11>" : "mul_ppg_kernel<17>";
     return "";
 }
 
-// launch_mul_mfma, leaf = false (mul_mfma.hip:637-645): `a.umax <= kMfTinyWords` -> the tiny
-// instance <false,true,false,11>, `a.umax <= kMfNarrowWords` -> the narrow one
-// <false,true,false,17,16>, `a.lean` -> the windowed wide one <false,true,true>, else <false>
+// launch_mul_mfma, leaf = false: `a.umax <= kMfTinyWords` -> the tiny instance
+// <false,true,false,11>, `a.umax <= kMfNarrowWords` -> the narrow one <false,true,false,17,16>,
+// `a.lean` -> the windowed wide one <false,true,true>, else <false>
 static const char *mf_instance(const hm::MfLaunch &m) {
     if (!m.nspans) return "";
     if (m.umax <= hm::kMfTinyWords) return "tiny";
     if (m.umax <= hm::kMfNarrowWords) return "narrow";
     return m.lean ? "wide_win" : "wide";
-}
-
-// run_ka (mul_host.cpp:829-838), the same expression: the lean leaf instance <true,true> for
-// leaves of kMfLeanLeafMin .. kMfLeanLeafWords words when 16 waves' slices fit a CU's LDS
-static bool lean_leaf(const hm::KaProg &pg) {
-    const uint32_t span = std::max(1u, (pg.leaf_omax + 31) / 32);
-    const uint32_t lw = hm::mul_mfma_lean_leaf_wave_words(pg.leaf_vmax, span, pg.leaf_umax);
-    return pg.leaf_umax <= hm::kMfLeanLeafWords && pg.leaf_umax >= hm::kMfLeanLeafMin &&
-           (256 + 4 * (size_t)lw) * 4 * 4 <= 160 * 1024;
 }
 
 static void put_launch(const hm::MfLaunch &m) {
@@ -96,7 +87,9 @@ int main(int argc, char **argv) {
         std::printf("],\n   \"ka\": [");
         for (size_t k = 0; k < c.ka.size(); ++k) {
             const hm::KaProg &pg = c.ka[k];
-            const bool lean = P.mfma && pg.nvtask && lean_leaf(pg);
+            hm::MulMfmaArgs leaves{};
+            hm::ka_leaf_launch(pg, leaves);
+            const bool lean = P.mfma && pg.nvtask && leaves.lean;
             std::printf("%s{\"lane\": %u, \"nvtask\": %u, \"leaf_umax\": %u, \"leaf_vmax\": %u, "
                         "\"leaf_omax\": %u, \"deg\": %d, \"lean_leaf\": %d}",
                         k ? ", " : "", pg.lane, pg.nvtask, pg.leaf_umax, pg.leaf_vmax, pg.leaf_omax,

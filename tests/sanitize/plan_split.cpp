@@ -1,12 +1,14 @@
-// Host-only check of the multiplier planner's split Karatsuba plans (mul_host.cpp, round 6), under
-// ASan/UBSan: the planner source is compiled into this driver (its planning functions are
-// internal), no hm_ctx and no GPU.  Built and run by tests/test_sanitize.py.
+// Host-only check of the multiplier planner's split Karatsuba plans and of its table image
+// (mul_plan.h), under ASan/UBSan: the planner header is compiled into this driver and nothing else
+// is linked, no hm_ctx and no GPU.  Built and run by tests/test_sanitize.py.
 //  - K = 16 with a 2^18-word scratch limit splits products into subtree programs, and the split
 //    plan issues exactly the leaf products of the breadth-first plan (the same multiset of leaf
 //    shapes), with every scratch region below the limit's bound;
 //  - K = 21 plans with the default limit (its largest product needs 3.1e8 scratch words
-//    breadth-first, past the 28-bit views), and K = 20's default plan is not split.
-#include "../../homomorph-rust_amd/csrc/mul_host.cpp"
+//    breadth-first, past the 28-bit views), and K = 20's default plan is not split;
+//  - pack_tables puts the K = 16 plan's 17 tables at 16-byte aligned offsets of the image, in
+//    order and in range, each holding the bytes of the vector it came from.
+#include "../../homomorph-rust_amd/csrc/mul_plan.h"
 
 #include <cstdio>
 #include <tuple>
@@ -41,6 +43,22 @@ static std::vector<std::tuple<uint32_t, uint32_t, uint32_t>> leaf_shapes(const h
     return v;
 }
 
+// the image pack_tables makes of a plan's tables
+static void check_image(hm::MulPlan &P) {
+    const std::vector<uint8_t> img = hm::pack_tables(P);
+    size_t ntables = 0, end = 0;
+    hm::for_each_table(P, [&](size_t off, const auto &v) {
+        const size_t n = hm::table_bytes(v);
+        CHECK(off % 16 == 0 && off >= end && off + n <= img.size());
+        CHECK(n == 0 || std::memcmp(img.data() + off, v.data(), n) == 0);
+        end = off + n;
+        ++ntables;
+    });
+    CHECK(ntables == 17);
+    CHECK(img.size() % 16 == 0 && img.size() >= 16 && img.size() < end + 16);
+    CHECK(P.off_slots == 0 && !P.slots.empty() && P.off_ka_combs > P.off_ka_vtiles);
+}
+
 int main() {
     hm::MulPlan whole, split;
     CHECK(plan(16, hm::kKaScratchWords, whole));
@@ -50,6 +68,8 @@ int main() {
     CHECK(whole.ka_vtasks.size() == split.ka_vtasks.size());
     CHECK(leaf_shapes(whole) == leaf_shapes(split));
     CHECK(split.astride < whole.astride); // less scratch per value
+    check_image(whole);
+    check_image(split);
     hm::MulPlan k20, k21;
     CHECK(plan(20, hm::kKaScratchWords, k20));
     CHECK(subprograms(k20) == 0);

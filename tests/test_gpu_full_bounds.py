@@ -268,7 +268,7 @@ def test_mul(H, world, name, products):
 @pytest.mark.parametrize("name", list(synth.MUL_CLASS_CASES))
 def test_mul_classes(H, world, name, products):
     """Every product class of the multiplier at its size edges, and the degree ladders that walk
-    the kernels' inner paths.  build_plan (mul_host.cpp) picks the launches from the static
+    the kernels' inner paths.  build_plan (mul_plan.h) picks the launches from the static
     bounds; the kernels pick their path from each operand's word count nu (from its degree).
     u8 operands, uniform bounds a / b unless noted, mul_low(4) unless noted; paths from the
     planner's own census (synth.check_mul_class_path, test_synth_reference.py):

@@ -6,10 +6,11 @@ engine library's host code, run on the CPU (GPU sanitizers are not available on 
 - tests/sanitize/capi_san.cpp: every host-only C-ABI entry point (status strings, bounds, the
   multiplier cost model, strides, the wire-format parser under 20k corrupted headers, NULL
   contexts), with the device kernels linked in unsanitised;
-- tests/sanitize/plan_split.cpp: the multiplier planner's split Karatsuba plans (host only): the
-  same leaf products as the breadth-first plans at K = 16, K = 21 planned;
-- tests/sanitize/plan_census.cpp: one plan's launches and sizes as JSON (host only), the source of
-  the full-bounds tier's multiplier path assertions (tests/synth.py mul_census);
+- tests/sanitize/plan_split.cpp: the multiplier planner (mul_plan.h, host only, nothing linked):
+  its split Karatsuba plans, the same leaf products as the breadth-first plans at K = 16, K = 21
+  planned, and the byte image of a plan's tables (aligned offsets, equal bytes);
+- tests/sanitize/plan_census.cpp: one plan's launches and sizes as JSON (mul_plan.h, host only),
+  the source of the full-bounds tier's multiplier path assertions (tests/synth.py mul_census);
 - tests/sanitize/add_census.cpp: one adder plan (add_host.h plan_add) as JSON, the planner
   compiled alone into the driver (tests/synth.py add_census, tests/test_add_plans.py);
 - tests/sanitize/capi_oom.cpp (not sanitised): every allocation inside the multiplier's plan
