@@ -644,6 +644,12 @@ hm_status hm_ctx_set_mul_scratch(hm_ctx *c, uint64_t words) try {
     return HM_OK;
 } HM_ABI_CATCH
 
+hm_status hm_ctx_set_mul_chunk(hm_ctx *c, uint64_t max_values) try {
+    if (!c) return HM_ERR_INVALID_ARGUMENT;
+    c->mul_chunk = max_values;
+    return HM_OK;
+} HM_ABI_CATCH
+
 hm_status hm_ctx_set_add_pipeline(hm_ctx *c, int enable) try {
     if (!c) return HM_ERR_INVALID_ARGUMENT;
     c->add_pipe = enable != 0;

@@ -74,6 +74,9 @@ struct hm_ctx {
     // Karatsuba scratch per value and lane above which a product is planned one subtree at a
     // time (hm_ctx_set_mul_scratch; mul_plan.h kKaScratchWords)
     uint64_t ka_scratch = hm::kKaScratchWords;
+    // most values of one chunk of a multiply (hm_ctx_set_mul_chunk, a test hook; 0 = no cap):
+    // not part of a plan's key
+    uint64_t mul_chunk = 0;
     // where the Karatsuba leaf products run (hm_ctx_set_mul_products): HM_MUL_PRODUCTS_*
     uint32_t mul_products = 0;
     // carry chain of the adder (hm_ctx_set_add_options): HM_ADD_CHAIN_AUTO / _MFMA / _VALU

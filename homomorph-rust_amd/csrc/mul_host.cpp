@@ -4,7 +4,10 @@
 // planner mul_plan.h; here plans are uploaded and cached per context, keyed by the operand bounds
 // and the context's multiplier options (get_plan), and run (mul_columns: per chunk of values the
 // staging, the grouped partial products, then per column partial products, prefix scan and carry
-// products, and the final copy-out).
+// products, and the final copy-out).  A chunk holds as many values as fit half of the free device
+// memory, so on an empty device every batch is one chunk; the chunk loop itself (e0 > 0, a short
+// last chunk, an arena last written by another chunk) runs under hm_ctx_set_mul_chunk, a test hook
+// (tests/test_gpu_mul_chunks.py).
 #include <algorithm>
 #include <memory>
 
@@ -243,7 +246,8 @@ hm_status mul_columns(hm_ctx *c, const hm_batch *a, const hm_batch *b, uint32_t 
     size_t freeb = 0, totalb = 0;
     HM_HIP(c, hipMemGetInfo(&freeb, &totalb));
     const uint64_t budget = std::max<uint64_t>((uint64_t)(freeb + c->mws_bytes) / 2, 1ull << 28);
-    const uint64_t chunk = std::min<uint64_t>(a->n, budget / per_value);
+    uint64_t chunk = std::min<uint64_t>(a->n, budget / per_value);
+    if (c->mul_chunk) chunk = std::min(chunk, c->mul_chunk); // (a zero chunk stays refused below)
     if (chunk == 0) return HM_ERR_UNSUPPORTED;
     const uint64_t arena_words = ((P->astride * chunk) + 63) & ~(uint64_t)63;
     HM_HIP(c, grow(c, c->d_mws, c->mws_bytes, (size_t)(arena_words + nslots * chunk) * 4));

@@ -848,6 +848,12 @@ class Context:
         either way."""
         _check(lib().hm_ctx_set_mul_scratch(self._h, words_per_value), "hm_ctx_set_mul_scratch")
 
+    def set_mul_chunk(self, max_values: int = 0):
+        """hm_ctx_set_mul_chunk (a test hook): at most max_values values in one chunk of a
+        multiply, 0 (the default) = as many as the memory budget allows.  Results are identical
+        either way."""
+        _check(lib().hm_ctx_set_mul_chunk(self._h, int(max_values)), "hm_ctx_set_mul_chunk")
+
     MUL_PRODUCTS = {"auto": 0, "mfma": 1, "valu": 2}
 
     def set_mul_products(self, products: str = "auto"):

@@ -82,6 +82,7 @@ SIGNATURES = {
     "hm_validate_operation_bits": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_uint32, u16p]),
     "hm_ctx_set_mul_options": (ctypes.c_int, [vp, ctypes.c_uint32, ctypes.c_uint32]),
     "hm_ctx_set_mul_scratch": (ctypes.c_int, [vp, ctypes.c_uint64]),
+    "hm_ctx_set_mul_chunk": (ctypes.c_int, [vp, ctypes.c_uint64]),
     "hm_ctx_set_add_options": (ctypes.c_int, [vp, ctypes.c_uint32]),
     "hm_ctx_set_mul_products": (ctypes.c_int, [vp, ctypes.c_uint32]),
     "hm_ctx_set_add_pipeline": (ctypes.c_int, [vp, ctypes.c_int]),

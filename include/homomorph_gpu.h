@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define HM_ABI_VERSION 11 /* 4: kernel timing by device stamps (HM_TIME_*), hm_ctx_last_hip_error;
+#define HM_ABI_VERSION 12 /* 4: kernel timing by device stamps (HM_TIME_*), hm_ctx_last_hip_error;
                             5: hm_ctx_clear_kernel_timing, hm_ctx_set_mul_scratch;
                             6: HM_OP_SUB .. HM_OP_GE, hm_sub_batch, hm_compare_batch, their bounds,
                                hm_validate_operation_bits;
@@ -45,7 +45,8 @@ extern "C" {
                             10: HM_OP_COUNT_ONES .. HM_OP_TRAILING_ONES, hm_bitcount_batch,
                                hm_bitcount_out_bounds;
                             11: HM_OP_ARRAY_READ, HM_OP_ARRAY_WRITE, hm_array_read_batch,
-                               hm_array_write_batch, their bounds */
+                               hm_array_write_batch, their bounds;
+                            12: hm_ctx_set_mul_chunk */
 #define HM_MAX_BITS 128 /* u128 is the widest type with impls (src/impls/numbers/uint.rs:58) */
 
 typedef enum hm_status {
@@ -235,6 +236,15 @@ hm_status hm_ctx_set_mul_options(hm_ctx *ctx, uint32_t karatsuba_min_words,
  * product up to the u32 multiply's K = 20 prefix runs whole; K = 21..24 need the split).  At most
  * 2^27 + 2^26 words (the plan's views hold 28-bit offsets); at least 1. */
 hm_status hm_ctx_set_mul_scratch(hm_ctx *ctx, uint64_t words_per_value);
+/* Chunk limit of the multiplier (no effect on results).  hm_ctx_set_mul_chunk is a TEST hook, like
+ * hm_ctx_seed_rng.  A multiply runs its n values in chunks that share one workspace: by default a
+ * chunk holds as many values as fit half of the free device memory (at least 2^28 bytes), so on an
+ * otherwise empty device every batch is one chunk, and how many chunks a batch takes depends on
+ * what else runs on the card.  max_values > 0 caps the chunk, chunk = min(n, budget / per_value,
+ * max_values), so that tests run the chunk loop at sizes of their choosing; 0 (the default) is no
+ * cap.  Cached plans do not depend on it.  The workspace is sized for the chunk (it never shrinks
+ * while the context lives, and is replaced as every other workspace is: hm_ctx_generation). */
+hm_status hm_ctx_set_mul_chunk(hm_ctx *ctx, uint64_t max_values);
 
 /* Where the multiplier's products run (no effect on results: every product is exact): as {0,1}
  * Toeplitz GEMMs on the fp4 matrix cores (MFMA, reduced mod 2) or as VALU products.  The choice
@@ -446,7 +456,9 @@ hm_status hm_mul_batch(hm_ctx *ctx, const hm_batch *a, const hm_batch *b, int is
  * circuit on the low k bits, bit for bit.  The signed circuit (:115-155) differs from the
  * unsigned one only in column nbits-1, so for k < nbits this is also the signed product's low
  * bits.  a, b: nbits-bit batches read in place; out: k bits, bounds from hm_mul_out_bounds over
- * the first k input bounds.  Same requirement as HM_OP_MUL (d >= 64 delta). */
+ * the first k input bounds.  Same requirement as HM_OP_MUL (d >= 64 delta).  Only input bits
+ * 0..k-1 of a and b are read and validated: bits k..nbits-1 are not looked at (a corrupted degree
+ * word or limb there raises no HM_ERR_BAD_INPUT). */
 hm_status hm_mul_low_batch(hm_ctx *ctx, const hm_batch *a, const hm_batch *b, uint32_t k,
                            hm_batch *out);
 /* Context::apply2::<HomomorphicAnd/Or/XorGate> and apply1::<HomomorphicNotGate> (common.rs:5-35,

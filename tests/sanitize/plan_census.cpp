@@ -73,7 +73,9 @@ int main(int argc, char **argv) {
     std::printf(" \"cols\": [\n");
     for (uint32_t i = 0; i < P.K; ++i) {
         const hm::MulPlan::Col &c = P.cols[i];
-        std::printf("  {\"npp\": %u, \"ppl\": ", c.npp);
+        // (nitems: the scan's items, which launch_mul_scan stages in LDS; maxwords: its widest prefix)
+        std::printf("  {\"npp\": %u, \"nitems\": %u, \"maxwords\": %u, \"ppl\": ", c.npp, c.nitems,
+                    c.maxwords);
         put_launch(c.ppl);
         std::printf(",\n   \"nrows\": %u, \"rows_uw\": %u, \"rows_vw\": %u, \"rows_ow\": %u, \"rows_qw\": %u,\n",
                     c.nrows, c.rows_uw, c.rows_vw, c.rows_ow, c.rows_qw);

@@ -1975,3 +1975,270 @@ def check_array_path(name):
 
 _WAVE_FAMILIES = {"select": _select_inputs, "minmax": _minmax_inputs, "lookup": _lookup_inputs,
                   "shift": _shift_inputs, "count": _count_inputs, "array": _array_inputs}
+
+
+# =============================================================================================
+# The multiplier's chunk loop, its staging checks and the plans with K > 32
+# (test_gpu_mul_chunks.py).  mul_columns (mul_host.cpp) cuts a batch into chunks of
+# values that share one workspace; hm_ctx_set_mul_chunk caps the chunk, so that e0 > 0, a short
+# last chunk and an arena last written by longer operands are met at batches of 10 values.
+
+# The smallest case per launch family, (family, name): run chunked against the unchunked references
+# above (mul_reference, mul_class_reference).
+CHUNK_CASES = (
+    ("mul", "u8_b128"), ("mul", "i8_b128"), ("mul", "u16_low4_per_bit"),
+    ("mulc", "ppv_12w"), ("mulc", "ppg_tiny_13w"), ("mulc", "ppg_gen_33w"), ("mulc", "rows_v36"),
+    ("mulc", "ppm_wide"), ("mulc", "u8_b640_full"), ("mulc", "u8_b703_ka224"),
+)
+STALE_LADDERS = ("ladder_ppg_gen", "ladder_ppm", "ladder_rows")
+
+
+def mul_spec(family, name):
+    """dict(k, signed, ka) of a "mul" or "mulc" case, and its reference function."""
+    if family == "mul":
+        _, _, signed, k, _, _ = MUL_CASES[name]
+        return dict(k=k, signed=signed, ka=None), mul_reference
+    spec = MUL_CLASS_CASES[name]
+    return dict(k=spec["k"], signed=spec["signed"], ka=spec["ka"]), mul_class_reference
+
+
+@functools.lru_cache(maxsize=None)
+def descending(name):
+    """A ladder with its values in descending order (the widest a_i first), operands and reference
+    rows permuted alike: (la, da, lb, db, out bounds, rl, rd).  Every chunk after the first then
+    meets arena slots last written by longer operands."""
+    c = inputs("mulc", name)
+    ob, vals, _, _ = mul_class_reference(name)
+    perm = list(range(c["n"]))[::-1]
+    words_a = [words(c["A"][e][0]) for e in perm]
+    assert words_a == sorted(words_a, reverse=True) and words_a[0] > words_a[-1]
+    la, da = bm.pack([c["A"][e] for e in perm], c["ba"])
+    lb, db = bm.pack([c["B"][e] for e in perm], c["bb"])
+    return (la, da, lb, db, ob) + _frozen(*bm.pack([vals[e] for e in perm], ob))
+
+
+STALE_BLOCK = 4
+
+
+@functools.lru_cache(maxsize=None)
+def interleaved(name):
+    """16 values over a ladder case's bounds (mul_low(3)), in blocks of STALE_BLOCK: every bit of a
+    and b FULL; then a NULL under b FULL and a FULL over b NULL, two values each (every partial
+    product null); FULL again; then a = b = UNIT in two values, a UNIT under b FULL, a FULL over
+    b UNIT (products of one word, or copies of the other operand).  With a chunk of STALE_BLOCK
+    values, chunks of full operands alternate with chunks whose every product is null or short, in
+    the slots the full ones filled.  dict(A, B, ba, bb, n, ob, vals) + packed operands and
+    reference."""
+    c = inputs("mulc", name)
+    ba, bb, k = c["ba"], c["bb"], MUL_CLASS_CASES[name]["k"]
+    rng = np.random.default_rng(_seed("interleaved", name))
+    full = lambda bnd: [_exact(rng, int(b)) for b in bnd]  # noqa: E731
+    null, unit = [0] * len(ba), [1] * len(ba)
+    A = [full(ba) for _ in range(4)] + [null, null, full(ba), full(ba)] + \
+        [full(ba) for _ in range(4)] + [unit, unit, unit, full(ba)]
+    B = [full(bb) for _ in range(4)] + [full(bb), full(bb), null, null] + \
+        [full(bb) for _ in range(4)] + [unit, unit, full(bb), unit]
+    ob = mul_bounds(ba[:k], bb[:k])
+    vals = [mul_ref(a[:k], b[:k]) for a, b in zip(A, B)]
+    assert all(v == [0] * k for v in vals[4:8]) and vals[12] == [1, 0, 0][:k]  # 7 * 7 = 49
+    return dict(A=A, B=B, ba=ba, bb=bb, n=16, k=k, ob=ob, vals=vals,
+                a=bm.pack(A, ba), b=bm.pack(B, bb), ref=_frozen(*bm.pack(vals, ob)))
+
+
+# ------------------------------------------------------------------ staging validation
+STAGE_BOUND, STAGE_N, STAGE_CHUNK = 383, 8, 3
+CORRUPTIONS = ("bit_above_degree", "degree_above_bound", "top_bit_cleared", "limb_past_degree")
+
+
+@functools.lru_cache(maxsize=None)
+def stage_inputs():
+    """The clean batch of the staging-validation tests: u8 at the uniform bound 383 (the ppv plan:
+    mul_stage_value_kernel, 6 limbs per bit), the 8 scheduled values."""
+    ba = uniform(8, STAGE_BOUND)
+    A, B = batch(ba, ba, STAGE_N, 0, _seed("stage", "u8_b383"))
+    return dict(ba=ba, bb=ba, A=A, B=B, n=STAGE_N, nbits=8, a=bm.pack(A, ba), b=bm.pack(B, ba))
+
+
+@functools.lru_cache(maxsize=None)
+def stage_reference(what):
+    """what: "low4" (mul_low(4)), "full" (the unsigned multiply), "and", "not"."""
+    c = stage_inputs()
+    if what in ("low4", "full"):
+        k = 4 if what == "low4" else 8
+        ob = mul_bounds(c["ba"][:k], c["bb"][:k])
+        vals = [mul_ref(a[:k], b[:k]) for a, b in zip(c["A"], c["B"])]
+    else:
+        ob = gate_bounds(what, c["ba"], c["bb"])
+        vals = [gate_circuit(what, a, b) for a, b in zip(c["A"], c["B"])]
+    return (ob, vals) + _frozen(*bm.pack(vals, ob))
+
+
+def corruptible(p, bound, how):
+    """Whether polynomial p of a bit of this bound can take the corruption inside the bit's own
+    limbs: bit_above_degree sets coefficient deg + 1 in the degree's limb; top_bit_cleared needs a
+    top coefficient that the degree word is checked against (deg > 0); limb_past_degree sets a
+    coefficient in the bit's last limb, which must lie past the degree's limb."""
+    d, cap = model.degree(p), int(bound) // 64 + 1
+    if how == "bit_above_degree":
+        return (d + 1) % 64 != 0 and d + 1 <= int(bound)
+    if how == "top_bit_cleared":
+        return d > 0
+    if how == "limb_past_degree":
+        return d // 64 < cap - 1
+    return how == "degree_above_bound"
+
+
+def corruption_site(values, bound, how, bits, first=STAGE_CHUNK):
+    """The first (value e >= first, bit i in bits) whose polynomial can take the corruption: with a
+    chunk of `first` values the corrupted value is in a chunk with e0 > 0.  A polynomial of degree
+    above 0 where there is one, else a null or unit one."""
+    for nonconstant in (True, False):
+        for e in range(first, len(values)):
+            for i in bits:
+                p = values[e][i]
+                if corruptible(p, bound[i], how) and (p > 1 or not nonconstant):
+                    return e, i
+    raise LookupError(how)
+
+
+def corrupt(limbs, deg, bound, n, e, i, how):
+    """A copy of the packed batch with one corruption in value e, bit i.  Every write stays inside
+    that bit's own cap limbs and its own degree word."""
+    bound = u32(bound)
+    cap = (bound // 64 + 1).astype(np.int64)
+    limbs, deg = limbs.copy(), deg.copy().reshape(n, len(bound))
+    base = e * int(cap.sum()) + int(cap[:i].sum())
+    d, last = int(deg[e, i]), base + int(cap[i]) - 1
+    if how == "bit_above_degree":
+        g = base + (d + 1) // 64
+        assert g == base + d // 64 <= last
+        limbs[g] |= np.uint64(1 << ((d + 1) % 64))
+    elif how == "degree_above_bound":
+        deg[e, i] = int(bound[i]) + 1
+    elif how == "top_bit_cleared":
+        assert d > 0
+        limbs[base + d // 64] &= np.uint64(~(1 << (d % 64)) & (2**64 - 1))
+    elif how == "limb_past_degree":
+        assert base + d // 64 < last
+        limbs[last] |= np.uint64(1 << 7)
+    else:
+        raise KeyError(how)
+    return limbs, deg.reshape(-1)
+
+
+# ------------------------------------------------------------------ plans with K > 32
+# u64 operands whose every bit has bound 0: each ciphertext bit is the null or the unit polynomial,
+# the only bounds at which build_plan (mul_plan.h) accepts K > 32 at a size a test can run.  2 K > 64
+# takes launch_mul_stage off mul_stage_value_kernel, onto mul_stage_kernel (one wave per (value,
+# bit)).  name -> (K, signed); K = 64 is the full circuit.
+WIDE_CASES = {"low33": (33, False), "low40": (40, False), "full64": (64, False),
+              "full64_signed": (64, True)}
+WIDE_ASTRIDE = {33: 6352, 40: 9376, 64: 24208}  # arena words per value
+_M64 = (1 << 64) - 1
+
+
+@functools.lru_cache(maxsize=None)
+def wide_values():
+    """The six (a, b) pairs as integers: all NULL under all UNIT, all UNIT twice, alternating bits
+    against their complement, two random patterns (one against an all-NULL b), 2^63 + 1 squared."""
+    rng = np.random.default_rng(_seed("wide", "u64_b0"))
+    r = [_rand_bits(rng, 64) for _ in range(3)]
+    alt = int("AA" * 8, 16)
+    top = (1 << 63) | 1
+    return ((0, _M64), (_M64, _M64), (alt, alt >> 1), (r[0], r[1]), (r[2], 0), (top, top))
+
+
+def _bits64(v):
+    return [(v >> i) & 1 for i in range(64)]
+
+
+@functools.lru_cache(maxsize=None)
+def wide_inputs():
+    ba = uniform(64, 0)
+    A = [_bits64(a) for a, _ in wide_values()]
+    B = [_bits64(b) for _, b in wide_values()]
+    return dict(ba=ba, bb=ba, A=A, B=B, n=len(A), nbits=64, a=bm.pack(A, ba), b=bm.pack(B, ba))
+
+
+@functools.lru_cache(maxsize=None)
+def wide_reference(name):
+    """(out bounds, values, limbs, degree words) of the model's K-bit circuit on the low K bits."""
+    K, signed = WIDE_CASES[name]
+    c = wide_inputs()
+    ob = mul_bounds(c["ba"][:K], c["bb"][:K])
+    vals = [mul_ref(a[:K], b[:K], signed) for a, b in zip(c["A"], c["B"])]
+    return (ob, vals) + _frozen(*bm.pack(vals, ob))
+
+
+def wide_census(name, mfma=True, ba=None):
+    K, signed = WIDE_CASES[name]
+    b = tuple(int(x) for x in (wide_inputs()["ba"] if ba is None else ba)[:K])
+    return plan_census(64, K, signed and K == 64, 256, 256, mfma, b, tuple([0] * K))
+
+
+def check_mul_wide_path(name):
+    """The path of a WIDE_CASES case from the planner's census: K > 32 (so 2 K > 64 and
+    launch_mul_stage takes mul_stage_kernel), the arena stride, where the K (K + 1) / 2 partial
+    products run, and every column's scan: column i has its i + 1 partial products and the carries
+    of the column before, one per item but the first, so 1 + i (i + 1) / 2 items; the scan stages
+    20 bytes per item in LDS (launch_mul_scan: at most 64 KiB)."""
+    K, signed = WIDE_CASES[name]
+    assert K > 32 and 2 * K > 64
+    flip = signed and K == 64
+    for mfma in (True, False):
+        cen = wide_census(name, mfma)
+        cols = cen["cols"]
+        assert cen["K"] == K and len(cols) == K and bool(cen["signed"]) == flip
+        assert cen["astride"] == WIDE_ASTRIDE[K] < 10**5
+        assert not cen["ppg"] and not cen["ppv"] and cen["pp_instance"] == ""  # no grouped launch
+        nitems = [col["nitems"] for col in cols]
+        assert nitems == [1 + i * (i + 1) // 2 for i in range(K)]
+        assert 20 * max(nitems) <= 64 * 1024
+        assert {col["res_bound"] for col in cols} == {0} and {col["maxwords"] for col in cols} == {4}
+        assert not any(col["ka"] for col in cols)
+        vpp = [col["npp"] for col in cols]       # partial products on mul_pp_kernel
+        mpp = [col["ppl"]["nspans"] for col in cols]  # ... and on the matrix cores
+        if mfma:  # the signed corners a_0 b_63 + 1 and a_63 b_0 + 1 stay on the VALU
+            assert vpp == [0] * (K - 1) + [2 if flip else 0]
+            assert mpp == [i + 1 for i in range(K - 1)] + [K - (2 if flip else 0)]
+            assert all(_launch(col["ppl"], "tiny", 4, 4) for col in cols[:K - 1])
+            # carry products, i (i + 1) / 2 in column i < K - 1 (4 x 4 words each): one
+            # mul_rows_kernel launch up to column 28's 406, one launch on the tiny MFMA instance
+            # from column 29's 435 on, where the rows no longer fit a wave's share of LDS
+            for i, col in enumerate(cols):
+                c = i * (i + 1) // 2 if i + 1 < K else 0
+                tiny = col["mfl"][0]
+                assert (col["nrows"], tiny["nspans"]) == ((c, 0) if i <= 28 else (0, c)), i
+                assert not c or i <= 28 or _launch(tiny, "tiny", 4, 4)
+                assert not col["mfl"][1]["nspans"] and not col["mfl"][2]["nspans"]
+        else:
+            assert vpp == [i + 1 for i in range(K)] and not any(mpp)
+            assert not any(col["nrows"] for col in cols)
+            assert not any(m["nspans"] for col in cols for m in col["mfl"])
+            # one W = 1 tile per carry product: none in column 0, none pushed by the last column
+            # of the full circuit
+            carries = sum(n - 1 for n in nitems[:K - 1])
+            assert sum(col["ntiles"][0] for col in cols) == carries
+    return cen
+
+
+# One bit of a wider bound among the bound-0 bits of the K = 33 plan: a_32 at bound 64 (two limbs,
+# read by column 32 alone, which pushes no carries), so that stage_one's check of the limbs past the
+# degree's limb has a limb to look at.
+WIDE_STAGE_BIT, WIDE_STAGE_BOUND = 32, 64
+
+
+@functools.lru_cache(maxsize=None)
+def wide_stage_inputs():
+    c = wide_inputs()
+    ba = c["ba"].copy()
+    ba[WIDE_STAGE_BIT] = WIDE_STAGE_BOUND
+    rng = np.random.default_rng(_seed("wide", "stage"))
+    A = [list(v) for v in c["A"]]
+    for e, v in enumerate(A):  # degrees 0 .. 64 at the wide bit: the degree's limb is the first or the second
+        v[WIDE_STAGE_BIT] = (0, 1, _exact(rng, 5), _exact(rng, 63), _exact(rng, 64), _exact(rng, 40))[e]
+    K = WIDE_CASES["low33"][0]
+    ob = mul_bounds(ba[:K], c["bb"][:K])
+    vals = [mul_ref(a[:K], b[:K]) for a, b in zip(A, c["B"])]
+    return dict(ba=ba, bb=c["bb"], A=A, B=c["B"], n=c["n"], K=K, ob=ob, vals=vals,
+                a=bm.pack(A, ba), b=c["b"], ref=_frozen(*bm.pack(vals, ob)))

@@ -197,6 +197,137 @@ def test_mul_class_reference(H, oracle, name):
     assert_batches_equal(ml, md, ol, od, ob, len(pick), name)
 
 
+# ------------------------------------------------------------------ chunks, staging, K > 32
+@pytest.mark.parametrize("name", list(synth.WIDE_CASES))
+def test_mul_wide_reference(H, oracle, name):
+    """The plans with K > 32 on bound-0 u64 operands (test_gpu_mul_chunks.py): every bit is the
+    null or the unit polynomial, so the carry-save circuit is ordinary binary arithmetic, and the
+    model is held against it, not only against itself: every output polynomial is 0 or 1 and the
+    value they spell is a * b mod 2^K (the signed circuit: the wrapping i64 product, the same 64
+    bits).  The model equals the bit-serial oracle on the same operands, the output bounds (all 0)
+    are hm_mul_out_bounds', and the path holds in the planner's census."""
+    from helpers import low_bits
+    K, signed = synth.WIDE_CASES[name]
+    c = synth.wide_inputs()
+    assert c["n"] == 6 and c["nbits"] == 64 and not c["ba"].any()
+    ob, vals, rl, rd = synth.wide_reference(name)
+    assert np.array_equal(ob, H.mul_out_bounds(c["ba"][:K], c["bb"][:K], signed)) and not ob.any()
+    mask = (1 << K) - 1
+    for (a, b), res in zip(synth.wide_values(), vals):
+        assert len(res) == K and set(res) <= {0, 1}
+        got = sum(p << i for i, p in enumerate(res))
+        assert got == (a * b) & mask, (name, hex(a), hex(b))
+        if signed:
+            sa, sb = a - (a >> 63 << 64), b - (b >> 63 << 64)
+            assert -2**63 <= sa < 2**63 and got == (sa * sb) % 2**64
+    vs = synth.wide_values()
+    assert vs[0][0] == 0 and vs[1] == (2**64 - 1, 2**64 - 1) and vs[4][1] == 0
+    assert vs[2][0] ^ vs[2][1] == 2**64 - 1 and vs[5] == (2**63 + 1, 2**63 + 1)
+    la, da, ba = low_bits(*c["a"], c["ba"], c["n"], K)
+    lb, db, bb = low_bits(*c["b"], c["bb"], c["n"], K)
+    ol, od = oracle.mul_batch(la, da, ba, lb, db, bb, K, c["n"], ob, signed=signed)
+    assert_batches_equal(rl, rd, ol, od, ob, c["n"], name)
+    cen = synth.check_mul_wide_path(name)
+    assert [col["res_bound"] for col in cen["cols"]] == ob.tolist()
+
+
+def test_wide_stage_reference(H, oracle):
+    """The K = 33 plan with a_32 at bound 64 (synth.wide_stage_inputs): it builds within 10^5 arena
+    words per value on both product settings, its column 32 alone reads the wide bit, and the model
+    equals the oracle."""
+    from helpers import low_bits
+    c = synth.wide_stage_inputs()
+    K, i = c["K"], synth.WIDE_STAGE_BIT
+    assert np.array_equal(c["ob"], H.mul_out_bounds(c["ba"][:K], c["bb"][:K]))
+    assert c["ob"].tolist() == [0] * 32 + [64]
+    assert sorted(synth.model.degree(v[i]) for v in c["A"]) == [0, 0, 5, 40, 63, 64]
+    for mfma in (True, False):
+        cen = synth.wide_census("low33", mfma, c["ba"])
+        assert cen["astride"] < 10**5 and [col["res_bound"] for col in cen["cols"]] == c["ob"].tolist()
+    la, da, ba = low_bits(*c["a"], c["ba"], c["n"], K)
+    lb, db, bb = low_bits(*c["b"], c["bb"], c["n"], K)
+    ol, od = oracle.mul_batch(la, da, ba, lb, db, bb, K, c["n"], c["ob"])
+    assert_batches_equal(*c["ref"], ol, od, c["ob"], c["n"], "K = 33, a_32 at bound 64")
+    for how in synth.CORRUPTIONS:
+        e, _ = synth.corruption_site(c["A"], c["ba"], how, [i], first=4)
+        assert e >= 4
+
+
+def test_stage_references_and_corruptions(H, oracle):
+    """The staging-validation batch (u8 at 383, 8 scheduled values): its references equal the
+    oracle's; every corruption changes exactly one limb or one degree word of a value with index
+    >= 3, inside the bit's own limbs, and leaves a batch that load_bit's rules refuse."""
+    from helpers import low_bits, offsets
+    c = synth.stage_inputs()
+    n = c["n"]
+    for what, k in (("low4", 4), ("full", 8)):
+        ob, vals, rl, rd = synth.stage_reference(what)
+        assert np.array_equal(ob, H.mul_out_bounds(c["ba"][:k], c["bb"][:k]))
+        within(vals, ob)
+        la, da, ba = low_bits(*c["a"], c["ba"], n, k)
+        lb, db, bb = low_bits(*c["b"], c["bb"], n, k)
+        ol, od = oracle.mul_batch(la, da, ba, lb, db, bb, k, n, ob)
+        assert_batches_equal(rl, rd, ol, od, ob, n, what)
+    assert synth.mul_census("ppv_12w")["pp_instance"] == "mul_ppv_kernel"  # the plan at 383
+    for op in ("and", "not"):
+        ob, vals, rl, rd = synth.stage_reference(op)
+        ol, od = oracle.gate_batch(op, *c["a"], c["ba"], *c["b"], c["bb"], 8, n, ob)
+        assert_batches_equal(rl, rd, ol, od, ob, n, op)
+    cap, off = 6, offsets(c["ba"])[0]
+    stride = 8 * cap
+    for X in ("a", "b"):
+        l0, d0 = c[X]
+        for how in synth.CORRUPTIONS:
+            for bits in (range(4), [5], range(8)):
+                e, i = synth.corruption_site(c[X.upper()], c["ba"], how, bits)
+                assert e >= synth.STAGE_CHUNK and i in bits
+                l1, d1 = synth.corrupt(l0, d0, c["ba"], n, e, i, how)
+                dl, dd = np.flatnonzero(l0 != l1), np.flatnonzero(d0 != d1)
+                assert len(dl) + len(dd) == 1
+                base = e * stride + int(off[i])
+                assert all(base <= g < base + cap for g in dl) and all(g == e * 8 + i for g in dd)
+                # what load_bit checks, on the corrupted bit
+                p = synth.model.limbs_to_int(l1[base: base + cap])
+                d = int(d1[e * 8 + i])
+                assert d > synth.STAGE_BOUND or p.bit_length() - 1 > d or (d > 0 and not p >> d & 1)
+
+
+@pytest.mark.parametrize("name", synth.STALE_LADDERS)
+def test_stale_arena_references(H, oracle, name):
+    """The descending ladders are the ladder's own rows, permuted; the interleaved batch's model
+    equals the oracle, and its null and unit blocks are what they are named for."""
+    from helpers import low_bits
+    c = synth.inputs("mulc", name)
+    la, da, lb, db, ob, rl, rd = synth.descending(name)
+    _, _, fl, fd = synth.mul_class_reference(name)
+    n, k = c["n"], synth.MUL_CLASS_CASES[name]["k"]
+    stride = int((ob // 64 + 1).sum())
+    assert np.array_equal(rl.reshape(n, stride)[::-1], fl.reshape(n, stride))
+    assert np.array_equal(rd.reshape(n, k)[::-1], fd.reshape(n, k))
+    pa, pd, _, _ = synth.packed("mulc", name)
+    sa = pa.size // n
+    assert np.array_equal(la.reshape(n, sa)[::-1], pa.reshape(n, sa))
+    t = synth.interleaved(name)
+    assert t["n"] == 16 and np.array_equal(t["ob"], ob)
+    assert all(p == 0 for v in t["A"][4:6] + t["B"][6:8] for p in v)
+    assert all(p == 1 for v in t["A"][12:15] + t["B"][12:14] + t["B"][15:] for p in v)
+    for blk in (0, 8):
+        assert all(p.bit_length() - 1 == int(b) for v in t["A"][blk:blk + 4] for p, b in zip(v, t["ba"]))
+    xa, xd, ba = low_bits(*t["a"], t["ba"], 16, k)
+    xb, xe, bb = low_bits(*t["b"], t["bb"], 16, k)
+    ol, od = oracle.mul_batch(xa, xd, ba, xb, xe, bb, k, 16, ob)
+    assert_batches_equal(*t["ref"], ol, od, ob, 16, name)
+
+
+def test_chunk_cases_are_the_tier_s():
+    """Every chunked case is a case of the full-bounds tier with n = 10, so that chunks of 1, 3 and
+    4 give 10 chunks, 3 + 3 + 3 + 1 and 4 + 4 + 2."""
+    for family, name in synth.CHUNK_CASES:
+        assert synth.inputs(family, name)["n"] == 10
+        spec, ref = synth.mul_spec(family, name)
+        assert ref(name)[2].size and set(spec) == {"k", "signed", "ka"}
+
+
 # ------------------------------------------------------------------ decryption
 @pytest.mark.parametrize("name", list(synth.DEC_CASES))
 def test_dec_reference(oracle, name):
